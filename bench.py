@@ -1,6 +1,7 @@
 """Throughput of the FastSpeech2 + TacoSpawn training step on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
 
 ``--gpus N`` without a launcher (no WORLD_SIZE in the environment) starts N fresh child
@@ -12,7 +13,13 @@ backward, clip_grad_norm_, Adam + LR schedule, zero_grad) on a synthetic SYN-48 
 rank (B = 48, 128 phonemes x 512 frames padded) with inputs resident in HBM.
 value = valid mel frames of all ranks per second (max-over-ranks time, weak scaling).
 
-The JSON line also carries
+A plain run sets up, runs W warm-up steps, times K steps and prints the JSON line (metric,
+value, unit, ms_per_step, ..., step_roofline, final_loss).  ``--dump-outputs DIR`` then also
+writes what the last timed step returned (losses, GMM loss, gradient norm, every tensor of the
+model's output) as ``DIR/<name>.npy`` in float32; inputs and weights are seeded, so two builds
+run with the same arguments can be compared array by array.
+
+With ``--full`` the JSON line also carries
   roofline      the DOMINANT launch set of the step by in-step time: HIP events (on the
                 stream each launch runs on, the weight-gradient side stream included) around
                 every GEMM / conv / attention launch of the last 3 warm-up steps, grouped by
@@ -24,7 +31,7 @@ The JSON line also carries
                 decoder's forward and backward (its weight-gradient stream joined) in extra
                 steps after the timed region, / 6 layers, against SURVEY §8d's 463.9 GFLOP
                 (padded shapes) and the valid-frame FLOP;
-  step_roofline the whole step: 3,904.7 GFLOP (§8d, padded) / ms_per_step;
+  step_roofline the whole step: 3,904.7 GFLOP (§8d, padded) / ms_per_step (plain runs too);
   f32           (bf16 runs, N = 1) the same step at the reference's precision (fp32);
   cpu_baseline  the CPU oracle (oracle/fs2_cpu.py, a restatement of the reference step) timed
                 on this host's cores: median of 3 steps after 1 warm-up (rank 0, N = 1 only).
@@ -506,6 +513,40 @@ def build_trainer(M, TR, dtype, dev, rank, graph=False, data_parallel=None):
     return model, TR.Trainer(model, pp, mc, tc, graph=graph, data_parallel=data_parallel), tc
 
 
+DUMP_BUDGET = 64 * 2 ** 20  # bytes of .npy payload per --dump-outputs directory, at most
+
+
+def _named_tensors(prefix, v, out):
+    if torch.is_tensor(v):
+        out.append((prefix, v))
+    elif isinstance(v, (int, float)):
+        out.append((prefix, torch.tensor(float(v))))
+    elif isinstance(v, (tuple, list)):
+        for i, x in enumerate(v):
+            _named_tensors(f"{prefix}_{i}", x, out)
+
+
+def dump_outputs(path, res):
+    """What ``Trainer.step`` returned -- (losses, GMM loss, gradient norm, model output[, the
+    --use-clf triple]) -- as ``path/<name>.npy``, float32 (bool / integer tensors converted).
+    Everything is written whole while the total stays under DUMP_BUDGET; otherwise the arrays
+    above an equal share of it are cut to a fixed sample (sorted flat indices drawn with
+    ``numpy.random.default_rng(0)``), the same sample in every run."""
+    named = []
+    for name, v in zip(("loss", "gmm_loss", "grad_norm", "output", "clf"), res):
+        _named_tensors(name, v, named)
+    arrs = [(n, t.detach().to("cpu", torch.float32).numpy()) for n, t in named]
+    if sum(a.nbytes for _, a in arrs) > DUMP_BUDGET:
+        share = DUMP_BUDGET // len(arrs) // 4  # elements
+        rng = np.random.default_rng(0)
+        arrs = [(n, a if a.size <= share else
+                 a.reshape(-1)[np.sort(rng.choice(a.size, share, replace=False))])
+                for n, a in arrs]
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrs:
+        np.save(os.path.join(path, n + ".npy"), a)
+
+
 def launch_check(world, rank):
     """--launch-check: the rank set the launcher produced (gloo, CPU only)."""
     if world > 1:
@@ -528,6 +569,12 @@ def main():
     ap.add_argument("--batch", type=int, default=48)
     ap.add_argument("--src-len", type=int, default=128)
     ap.add_argument("--dtype", default="bf16", choices=["f32", "bf16"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline / fft_block / f32 / cpu_baseline legs (runs of "
+                         "their own around and after the timed steps); the --no-* options below "
+                         "drop single legs of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes")
@@ -544,6 +591,8 @@ def main():
     ap.add_argument("--probe-wgrad", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_roofline = args.no_traffic = args.no_f32 = True
     if args.probe_wgrad:
         probe_wgrad()
         return
@@ -650,12 +699,21 @@ def main():
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        losses = trainer.step(batch, **kw())[0]
+    last = None
+    for i in range(args.steps):
+        res = trainer.step(batch, **kw())
+        losses = res[0]
+        if args.dump_outputs and i == args.steps - 1:
+            last = res  # only the last step's results are held past their step
+        del res
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last)
+        del last
     timed = None
     if dom:
         # the dominant class alone, its launches between HIP events, over as many further steps

@@ -5,7 +5,7 @@
 #   bash scripts/gpu.sh tests [pytest args]          GPU tests (-m gpu)
 #   bash scripts/gpu.sh check <tag>                  tests + smoke + default bench + kernel-trace
 #                                                    profile of a short bench run
-#   bash scripts/gpu.sh bench <tag> [bench args]     one bench.py line
+#   bash scripts/gpu.sh bench <tag> [bench args]     one bench.py line (--full: every leg)
 #   bash scripts/gpu.sh ab <tag> <rounds> <envA> <envB> [<envC> ...] [-- bench args]
 #                                                    interleaved same-box bench A/B of environment
 #                                                    settings, e.g. "FS2_TUNE=19=-1" or "-" (none)
@@ -33,10 +33,10 @@ check)
   tail -2 $o/tests.log
   timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1 || fail smoke $o/smoke.log
   tail -3 $o/smoke.log
-  timeout -k 10 400 python -u bench.py > $o/bench.log 2>&1 || fail bench $o/bench.log
+  timeout -k 10 400 python -u bench.py --full > $o/bench.log 2>&1 || fail bench $o/bench.log
   tail -1 $o/bench.log | cut -c1-700
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $o/prof -o $tag --output-format csv \
-    -- python3 bench.py --no-cpu-baseline --no-traffic --no-f32 --steps 20 --warmup 5 \
+    -- python3 bench.py --full --no-cpu-baseline --no-traffic --no-f32 --steps 20 --warmup 5 \
     > $o/prof.log 2>&1 || fail profile $o/prof.log
   echo profile ok ;;
 bench)
@@ -51,7 +51,7 @@ ab)
   for r in $(seq $rounds); do
     for e in "${envs[@]}"; do
       if [ "$e" = "-" ]; then set_env=(); else set_env=($e); fi
-      env "${set_env[@]}" timeout -k 10 300 python -u bench.py --steps 30 --warmup 5 --no-cpu-baseline \
+      env "${set_env[@]}" timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 5 --no-cpu-baseline \
         --no-traffic --no-f32 "$@" > $o/ab.log 2>&1 || fail "ab $e" $o/ab.log
       tail -1 $o/ab.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); f=d.get('fft_block',{}); print('$e', d['ms_per_step'], 'ms', 'fft', f.get('fwd_ms_per_block'), f.get('bwd_ms_per_block'), f.get('frac_valid'))"
     done
@@ -59,7 +59,7 @@ ab)
 profile)
   tag=${1:-prof}; shift || true; o=gpurun_out/$tag; mkdir -p $o
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $o/prof -o $tag --output-format csv \
-    -- python3 bench.py --no-cpu-baseline --no-traffic --no-f32 --steps 20 --warmup 5 "$@" \
+    -- python3 bench.py --full --no-cpu-baseline --no-traffic --no-f32 --steps 20 --warmup 5 "$@" \
     > $o/prof.log 2>&1 || fail profile $o/prof.log
   tail -1 $o/prof.log | cut -c1-400
   python3 scripts/kstats.py "$(find $o/prof -name '*kernel_stats.csv' | head -1)" 25 30 || true ;;

@@ -135,6 +135,46 @@ def test_bench_rejects_world_size_mismatch():
     assert rc == 2 and out is None and "WORLD_SIZE=2" in err
 
 
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("fs2_bench", f"{REPO}/bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_dump_outputs_names_dtype_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every tensor (and number) a step returned lands as <name>.npy in float32;
+    small results whole and exact, results over the byte budget as the same sample each time."""
+    import os
+    bench = _load_bench()
+    g = torch.Generator().manual_seed(0)
+    mel = torch.randn(3, 40, 80, generator=g)
+    res = ([torch.tensor(1.5), torch.tensor(0.25, dtype=torch.float64)], torch.tensor(-2.0), 0.75,
+           (mel, mel.to(torch.bfloat16), None, torch.arange(6).reshape(3, 2), mel[:, :, 0] > 0))
+    bench.dump_outputs(str(tmp_path / "a"), res)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"loss_0", "loss_1", "gmm_loss", "grad_norm", "output_0", "output_1",
+                        "output_3", "output_4"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss_1"] == 0.25 and got["gmm_loss"] == -2.0 and got["grad_norm"] == 0.75
+    assert np.array_equal(got["output_0"], mel.numpy())
+    assert np.array_equal(got["output_1"], mel.to(torch.bfloat16).float().numpy())
+    assert np.array_equal(got["output_3"], np.arange(6, dtype=np.float32).reshape(3, 2))
+    assert np.array_equal(got["output_4"], (mel[:, :, 0] > 0).numpy().astype(np.float32))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 3000)  # 3000 float32 values in all
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    c = {f[:-4]: np.load(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")}
+    assert set(b) == set(got) and sum(a.nbytes for a in b.values()) <= 4 * 3000
+    assert all(np.array_equal(b[k], c[k]) for k in b)
+    assert np.array_equal(b["output_3"], got["output_3"])  # under its share: whole
+    assert b["output_0"].size == 3000 // 8  # over it: a sample of the share's size ...
+    assert np.all(np.isin(b["output_0"], got["output_0"]))  # ... drawn from the array
+
+
 def test_jsut_config_shapes():
     """BASELINE config 1 (config/JSUT/model.yaml:42-43): one speaker, one GMM component,
     gender-only metadata (width 2); the synthetic batch follows the config."""
