@@ -570,6 +570,27 @@ int fs2_lr_expand_fwd(const float* x, const int32_t* cum, int64_t batch, int64_t
 /* dx[b, i] = sum of dout[b, t] over the frames phoneme i was copied to (segmented, in order). */
 int fs2_lr_expand_bwd(const float* dout, const int32_t* cum, int64_t batch, int64_t src_len,
                       int64_t out_len, int d, float* dx, void* stream);
+/* LengthRegulator + frame-level pitch / energy embeddings + decoder position encoding in one
+ * pass over the (batch, out_len, d) frames (model/modules.py:128-148 with a feature at
+ * "frame_level", transformer/Models.py:166-168):
+ *   v    = x[b, src[b, t]], zero past mel_len[b]          -> pre  (nullable)
+ *   v   += p_table[bucketize(p_values[b, t], p_bins)]      -> mid  (nullable), p_idx (nullable)
+ *   v   += e_table[bucketize(e_values[b, t], e_bins)]         e_idx (nullable)
+ *   v   += posenc[t] for t < pos_len                       -> out fp32 / out_t bf16 (nullable)
+ * Plain fp32 adds in that order: bitwise fs2_lr_expand_fwd (no posenc) -> fs2_bucket_embed_fwd
+ * -> fs2_bucket_embed_fwd -> + posenc.  A NULL table skips its embedding (that feature is
+ * phoneme-level, or this call is an inference stage before its prediction exists).  The
+ * embeddings are added on padded frames too: pad_1D pads the targets with 0.0 and the masked
+ * predictions are 0.0, so a padded frame carries table[bucketize(0)] as in the reference.
+ * values: (batch, out_len), values_dtype FS2_F32 or 2 = f64.  pre / mid are the frame-level
+ * predictors' inputs in the compute dtype copy_dtype (FS2_F32 or FS2_BF16).              */
+int fs2_lr_expand_embed_fwd(const float* x, const int32_t* cum, int64_t batch, int64_t src_len,
+                            int64_t out_len, int d, const void* p_values, int p_values_dtype,
+                            const float* p_bins, int p_n_bins, const float* p_table,
+                            const void* e_values, int e_values_dtype, const float* e_bins,
+                            int e_n_bins, const float* e_table, const float* posenc,
+                            int64_t pos_len, int copy_dtype, void* pre, void* mid, float* out,
+                            void* out_t, int32_t* p_idx, int32_t* e_idx, void* stream);
 
 /* ---------------------------------------------------------------- losses, GMM
  * FastSpeech2Loss (model/loss.py:19-92): masked L1 (mel, postnet), masked MSE (pitch,
@@ -594,6 +615,28 @@ int fs2_fs2loss_bwd(const float* mel_out, const float* post_out, const float* me
                     int64_t batch, int64_t src_len, int64_t mel_len, int n_mel, const float* ws,
                     const float* g_losses, float* d_mel_out, float* d_post_out, float* d_p,
                     float* d_e, float* d_logd, void* stream);
+/* The same losses with a level per variance term (model/loss.py:51-63): p_frame / e_frame
+ * != 0 marks pitch / energy as "frame_level".  Such a term's predictions and targets are
+ * (batch, mel_len), selected by mel_pad, and its mean runs over the valid frames: the count
+ * the forward leaves in ws, or denoms[0] / n_mel when denoms is given (the phoneme count is
+ * not used for it).  A phoneme-level term is (batch, src_len) under src_pad as above; with
+ * both flags 0 these are fs2_fs2loss_fwd / _bwd.  Same workspace, same single launch plus
+ * finaliser, no host sync.                                                               */
+int fs2_fs2loss_level_fwd(const float* mel_out, const float* post_out, const float* mel_tgt,
+                          int64_t tgt_len, const float* p_pred, const float* e_pred,
+                          const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                          const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                          int64_t batch, int64_t src_len, int64_t mel_len, int n_mel,
+                          int p_frame, int e_frame, const float* denoms, float* losses,
+                          float* ws, int64_t ws_bytes, void* stream);
+int fs2_fs2loss_level_bwd(const float* mel_out, const float* post_out, const float* mel_tgt,
+                          int64_t tgt_len, const float* p_pred, const float* e_pred,
+                          const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                          const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                          int64_t batch, int64_t src_len, int64_t mel_len, int n_mel,
+                          int p_frame, int e_frame, const float* ws, const float* g_losses,
+                          float* d_mel_out, float* d_post_out, float* d_p, float* d_e,
+                          float* d_logd, void* stream);
 
 /* SpeakerMetaEncoder (model/fastspeech2.py:306-341): pi = softmax(W m + b),
  * sigma = softplus(W m + b), mu = W m + b.  sigma_pre saved for the backward.          */

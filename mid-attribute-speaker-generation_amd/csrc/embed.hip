@@ -266,6 +266,54 @@ __global__ void lr_expand(const float* x, const int32_t* cum, int64_t B, int64_t
   }
 }
 
+// Frame-level variance adaptor (modules.py:128-148): expand + pitch / energy embeddings +
+// position encoding in one pass.  A value is bucketized in double, which orders f32 and f64
+// values exactly as their own precision does (bins are f32: every conversion is exact).
+FS2_DEV int frame_bucket(const void* vals, int dtype, int64_t r, const float* bins, int nb) {
+  const double v = dtype == FS2_F32 ? (double)((const float*)vals)[r] : ((const double*)vals)[r];
+  return lower_bound<double>(bins, nb, v);
+}
+
+template <bool CB>  // CB: pre / mid are bf16 (else fp32)
+FS2_DEV void st4_copy(void* base, int64_t off, f32x4 v) {
+  if (CB) st4_bf16((unsigned short*)base + off, v);
+  else st4((float*)base + off, v);
+}
+
+template <bool CB>
+__global__ void lr_expand_embed(const float* x, const int32_t* cum, int64_t B, int64_t Ts,
+                                int64_t Tout, int d, const void* pv, int pdt, const float* pbins,
+                                int pnb, const float* ptab, const void* ev, int edt,
+                                const float* ebins, int enb, const float* etab, const float* pos,
+                                int64_t pos_len, void* pre, void* mid, float* out,
+                                unsigned short* out_t, int32_t* pidx, int32_t* eidx) {
+  const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (r >= B * Tout) return;
+  const int64_t b = r / Tout, t = r - b * Tout;
+  const int i = upper_bound_i32(cum + b * Ts, (int)Ts, t);
+  int kp = 0, ke = 0;
+  if (ptab) {
+    kp = frame_bucket(pv, pdt, r, pbins, pnb);
+    if (lane == 0 && pidx) pidx[r] = kp;
+  }
+  if (etab) {
+    ke = frame_bucket(ev, edt, r, ebins, enb);
+    if (lane == 0 && eidx) eidx[r] = ke;
+  }
+  const bool add_pos = pos && t < pos_len;
+  for (int c = 4 * lane; c < d; c += 256) {
+    f32x4 v = i < Ts ? ld4(x + (b * Ts + i) * d + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if (pre) st4_copy<CB>(pre, r * d + c, v);
+    if (ptab) v += ld4(ptab + (int64_t)kp * d + c);
+    if (mid) st4_copy<CB>(mid, r * d + c, v);
+    if (etab) v += ld4(etab + (int64_t)ke * d + c);
+    if (add_pos) v += ld4(pos + t * d + c);
+    if (out) st4(out + r * d + c, v);
+    if (out_t) st4_bf16(out_t + r * d + c, v);
+  }
+}
+
 __global__ void lr_expand_bwd(const float* dout, const int32_t* cum, int64_t B, int64_t Ts,
                               int64_t Tout, int d, float* dx) {
   const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -462,6 +510,41 @@ int fs2_lr_expand_fwd(const float* x, const int32_t* cum, int64_t batch, int64_t
   lr_expand<<<rows_grid(rows), 256, 0, as_stream(stream)>>>(x, cum, batch, src_len, out_len, d,
                                                             posenc, out, (unsigned short*)out_t);
   return launch_status("fs2_lr_expand_fwd");
+}
+
+int fs2_lr_expand_embed_fwd(const float* x, const int32_t* cum, int64_t batch, int64_t src_len,
+                            int64_t out_len, int d, const void* p_values, int p_values_dtype,
+                            const float* p_bins, int p_n_bins, const float* p_table,
+                            const void* e_values, int e_values_dtype, const float* e_bins,
+                            int e_n_bins, const float* e_table, const float* posenc,
+                            int64_t pos_len, int copy_dtype, void* pre, void* mid, float* out,
+                            void* out_t, int32_t* p_idx, int32_t* e_idx, void* stream) {
+  FS2_CHECK_ARG(d % 4 == 0, "fs2_lr_expand_embed_fwd: d must be a multiple of 4");
+  FS2_CHECK_ARG(src_len > 0 && x && cum, "fs2_lr_expand_embed_fwd: empty phoneme axis");
+  FS2_CHECK_ARG(copy_dtype == FS2_F32 || copy_dtype == FS2_BF16,
+                "fs2_lr_expand_embed_fwd: copy dtype %d", copy_dtype);
+  FS2_CHECK_ARG(!p_table || (p_values && p_bins && p_n_bins >= 0 &&
+                             (p_values_dtype == FS2_F32 || p_values_dtype == 2)),
+                "fs2_lr_expand_embed_fwd: pitch table without f32/f64 values and bins");
+  FS2_CHECK_ARG(!e_table || (e_values && e_bins && e_n_bins >= 0 &&
+                             (e_values_dtype == FS2_F32 || e_values_dtype == 2)),
+                "fs2_lr_expand_embed_fwd: energy table without f32/f64 values and bins");
+  FS2_CHECK_ARG(!posenc || (pos_len >= 0 && pos_len <= out_len),
+                "fs2_lr_expand_embed_fwd: pos_len outside [0, out_len]");
+  const int64_t rows = batch * out_len;
+  if (rows == 0) return FS2_OK;
+  hipStream_t st = as_stream(stream);
+  if (copy_dtype == FS2_BF16)
+    lr_expand_embed<true><<<rows_grid(rows), 256, 0, st>>>(
+        x, cum, batch, src_len, out_len, d, p_values, p_values_dtype, p_bins, p_n_bins, p_table,
+        e_values, e_values_dtype, e_bins, e_n_bins, e_table, posenc, pos_len, pre, mid, out,
+        (unsigned short*)out_t, p_idx, e_idx);
+  else
+    lr_expand_embed<false><<<rows_grid(rows), 256, 0, st>>>(
+        x, cum, batch, src_len, out_len, d, p_values, p_values_dtype, p_bins, p_n_bins, p_table,
+        e_values, e_values_dtype, e_bins, e_n_bins, e_table, posenc, pos_len, pre, mid, out,
+        (unsigned short*)out_t, p_idx, e_idx);
+  return launch_status("fs2_lr_expand_embed_fwd");
 }
 
 int fs2_lr_expand_bwd(const float* dout, const int32_t* cum, int64_t batch, int64_t src_len,

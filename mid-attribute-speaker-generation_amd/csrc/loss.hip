@@ -19,12 +19,14 @@ namespace fs2 {
 constexpr int LOSS_FR = 64;  // frames per mel block
 
 // partial layout per block: [mel_abs, post_abs, p_sq, e_sq, d_sq, mel_frames, src_count, 0]
+// p_frame / e_frame (model/loss.py:51-63): that term is (B, Tm) under mel_pad and is summed by
+// the frame blocks (thread f of a block takes frame f of its 64) instead of the phoneme block
 __global__ void fs2loss_partial(const float* mel_out, const float* post_out, const float* mel_tgt,
                                 int64_t tgt_len, const float* p_pred, const float* e_pred,
                                 const float* logd_pred, const float* p_tgt, const float* e_tgt,
                                 const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
                                 int64_t B, int64_t Ts, int64_t Tm, int n_mel, int64_t n_mel_blocks,
-                                float* part) {
+                                int p_frame, int e_frame, float* part) {
   __shared__ float red[8][4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float s[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -43,11 +45,22 @@ __global__ void fs2loss_partial(const float* mel_out, const float* post_out, con
         s[1] += fabsf(post_out[fr * n_mel + c] - tv);
       }
     }
+    const int64_t fv = fb + threadIdx.x;
+    if ((p_frame || e_frame) && threadIdx.x < LOSS_FR && fv < B * Tm && !mel_pad[fv]) {
+      if (p_frame) {
+        const float dp = p_pred[fv] - p_tgt[fv];
+        s[2] += dp * dp;
+      }
+      if (e_frame) {
+        const float de = e_pred[fv] - e_tgt[fv];
+        s[3] += de * de;
+      }
+    }
   } else {
     for (int64_t i = threadIdx.x; i < B * Ts; i += blockDim.x) {
       if (src_pad[i]) continue;
-      const float dp = p_pred[i] - p_tgt[i];
-      const float de = e_pred[i] - e_tgt[i];
+      const float dp = p_frame ? 0.f : p_pred[i] - p_tgt[i];
+      const float de = e_frame ? 0.f : e_pred[i] - e_tgt[i];
       const float dd = logd_pred[i] - logf((float)d_tgt[i] + 1.f);
       s[2] += dp * dp;
       s[3] += de * de;
@@ -67,12 +80,13 @@ __global__ void fs2loss_partial(const float* mel_out, const float* post_out, con
                         : 0.f;
 }
 
-// losses = [total, mel, post, pitch, energy, duration]; dens[0..1] = (mel elements, phonemes)
+// losses = [total, mel, post, pitch, energy, duration]; dens[0..2] = (mel elements, phonemes,
+// frames): a frame-level term is divided by the frame count
 // 8 sums x 32 lanes: lane j of sum k adds partials j, j+32, ... in double; lanes are then
 // added in lane order (deterministic)
 __global__ __launch_bounds__(256) void fs2loss_final(const float* part, int64_t np, int n_mel,
-                                                     const float* denoms, float* losses,
-                                                     float* dens) {
+                                                     const float* denoms, int p_frame,
+                                                     int e_frame, float* losses, float* dens) {
   __shared__ double red[8][33];
   const int k = threadIdx.x >> 5, j = threadIdx.x & 31;
   double v = 0.0;
@@ -85,10 +99,13 @@ __global__ __launch_bounds__(256) void fs2loss_final(const float* part, int64_t 
     for (int jj = 0; jj < 32; ++jj) s[kk] += red[kk][jj];
   const double dm = denoms ? denoms[0] : s[5] * n_mel;
   const double dsr = denoms ? denoms[1] : s[6];
+  const double dfr = denoms ? (double)denoms[0] / n_mel : s[5];
   dens[0] = (float)dm;
   dens[1] = (float)dsr;
+  dens[2] = (float)dfr;
   const float mel = (float)(s[0] / dm), post = (float)(s[1] / dm);
-  const float pl = (float)(s[2] / dsr), el = (float)(s[3] / dsr), dl = (float)(s[4] / dsr);
+  const float pl = (float)(s[2] / (p_frame ? dfr : dsr)), el = (float)(s[3] / (e_frame ? dfr : dsr));
+  const float dl = (float)(s[4] / dsr);
   losses[1] = mel;
   losses[2] = post;
   losses[3] = pl;
@@ -123,18 +140,31 @@ __global__ void fs2loss_bwd_mel(const float* mel_out, const float* post_out, con
 __global__ void fs2loss_bwd_var(const float* p_pred, const float* e_pred, const float* logd_pred,
                                 const float* p_tgt, const float* e_tgt, const int64_t* d_tgt,
                                 const uint8_t* src_pad, int64_t n, const float* dens,
-                                const float* g, float* d_p, float* d_e, float* d_d) {
+                                const float* g, int p_frame, int e_frame, float* d_p, float* d_e,
+                                float* d_d) {
   const float s = 2.f / dens[1];
   const float gpi = (g[0] + g[3]) * s, ge = (g[0] + g[4]) * s, gd = (g[0] + g[5]) * s;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    if (src_pad[i]) {
-      d_p[i] = d_e[i] = d_d[i] = 0.f;
-      continue;
-    }
-    d_p[i] = gpi * (p_pred[i] - p_tgt[i]);
-    d_e[i] = ge * (e_pred[i] - e_tgt[i]);
-    d_d[i] = gd * (logd_pred[i] - logf((float)d_tgt[i] + 1.f));
+    const bool pad = src_pad[i];
+    if (!p_frame) d_p[i] = pad ? 0.f : gpi * (p_pred[i] - p_tgt[i]);
+    if (!e_frame) d_e[i] = pad ? 0.f : ge * (e_pred[i] - e_tgt[i]);
+    d_d[i] = pad ? 0.f : gd * (logd_pred[i] - logf((float)d_tgt[i] + 1.f));
+  }
+}
+
+// the frame-level terms' gradients, (B, Tm) under mel_pad, mean over dens[2] valid frames
+__global__ void fs2loss_bwd_frame(const float* p_pred, const float* e_pred, const float* p_tgt,
+                                  const float* e_tgt, const uint8_t* mel_pad, int64_t n,
+                                  const float* dens, const float* g, int p_frame, int e_frame,
+                                  float* d_p, float* d_e) {
+  const float s = 2.f / dens[2];
+  const float gpi = (g[0] + g[3]) * s, ge = (g[0] + g[4]) * s;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const bool pad = mel_pad[i];
+    if (p_frame) d_p[i] = pad ? 0.f : gpi * (p_pred[i] - p_tgt[i]);
+    if (e_frame) d_e[i] = pad ? 0.f : ge * (e_pred[i] - e_tgt[i]);
   }
 }
 
@@ -399,31 +429,33 @@ int64_t fs2_fs2loss_ws_bytes(int64_t batch, int64_t mel_len) {
   return (loss_parts(batch, mel_len) * 8 + 4) * 4;
 }
 
-int fs2_fs2loss_fwd(const float* mel_out, const float* post_out, const float* mel_tgt,
-                     int64_t tgt_len, const float* p_pred, const float* e_pred,
-                     const float* logd_pred, const float* p_tgt, const float* e_tgt,
-                     const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
-                     int64_t batch, int64_t src_len, int64_t mel_len, int n_mel,
-                     const float* denoms, float* losses, float* ws, int64_t ws_bytes, void* stream) {
-  FS2_CHECK_ARG(tgt_len >= mel_len, "fs2_fs2loss_fwd: target shorter than prediction");
-  FS2_CHECK_ARG(ws_bytes >= fs2_fs2loss_ws_bytes(batch, mel_len), "fs2_fs2loss_fwd: workspace too small");
+static int loss_fwd(const char* who, const float* mel_out, const float* post_out,
+                    const float* mel_tgt, int64_t tgt_len, const float* p_pred, const float* e_pred,
+                    const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                    const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                    int64_t batch, int64_t src_len, int64_t mel_len, int n_mel, int p_frame,
+                    int e_frame, const float* denoms, float* losses, float* ws, int64_t ws_bytes,
+                    void* stream) {
+  FS2_CHECK_ARG(tgt_len >= mel_len, "%s: target shorter than prediction", who);
+  FS2_CHECK_ARG(ws_bytes >= fs2_fs2loss_ws_bytes(batch, mel_len), "%s: workspace too small", who);
   hipStream_t st = as_stream(stream);
   poison(ws, ws_bytes, st);
   const int64_t np = loss_parts(batch, mel_len);
   fs2loss_partial<<<(unsigned)np, 256, 0, st>>>(mel_out, post_out, mel_tgt, tgt_len, p_pred, e_pred,
                                                 logd_pred, p_tgt, e_tgt, d_tgt, src_pad, mel_pad,
-                                                batch, src_len, mel_len, n_mel, np - 1, ws);
-  fs2loss_final<<<1, 256, 0, st>>>(ws, np, n_mel, denoms, losses, ws + np * 8);
-  return launch_status("fs2_fs2loss_fwd");
+                                                batch, src_len, mel_len, n_mel, np - 1, p_frame,
+                                                e_frame, ws);
+  fs2loss_final<<<1, 256, 0, st>>>(ws, np, n_mel, denoms, p_frame, e_frame, losses, ws + np * 8);
+  return launch_status(who);
 }
 
-int fs2_fs2loss_bwd(const float* mel_out, const float* post_out, const float* mel_tgt,
-                     int64_t tgt_len, const float* p_pred, const float* e_pred,
-                     const float* logd_pred, const float* p_tgt, const float* e_tgt,
-                     const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
-                     int64_t batch, int64_t src_len, int64_t mel_len, int n_mel, const float* ws,
-                     const float* g_losses, float* d_mel_out, float* d_post_out, float* d_p,
-                     float* d_e, float* d_logd, void* stream) {
+static int loss_bwd(const char* who, const float* mel_out, const float* post_out,
+                    const float* mel_tgt, int64_t tgt_len, const float* p_pred, const float* e_pred,
+                    const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                    const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                    int64_t batch, int64_t src_len, int64_t mel_len, int n_mel, int p_frame,
+                    int e_frame, const float* ws, const float* g_losses, float* d_mel_out,
+                    float* d_post_out, float* d_p, float* d_e, float* d_logd, void* stream) {
   hipStream_t st = as_stream(stream);
   const float* dens = ws + loss_parts(batch, mel_len) * 8;
   const int64_t n = batch * mel_len * n_mel;
@@ -437,8 +469,65 @@ int fs2_fs2loss_bwd(const float* mel_out, const float* post_out, const float* me
   if (ns > 0)
     fs2loss_bwd_var<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(p_pred, e_pred, logd_pred, p_tgt,
                                                                   e_tgt, d_tgt, src_pad, ns, dens,
-                                                                  g_losses, d_p, d_e, d_logd);
-  return launch_status("fs2_fs2loss_bwd");
+                                                                  g_losses, p_frame, e_frame, d_p,
+                                                                  d_e, d_logd);
+  const int64_t nf = batch * mel_len;
+  if ((p_frame || e_frame) && nf > 0) {
+    int64_t fb = (nf + 255) / 256;
+    if (fb > 8192) fb = 8192;
+    fs2loss_bwd_frame<<<(unsigned)fb, 256, 0, st>>>(p_pred, e_pred, p_tgt, e_tgt, mel_pad, nf, dens,
+                                                    g_losses, p_frame, e_frame, d_p, d_e);
+  }
+  return launch_status(who);
+}
+
+int fs2_fs2loss_fwd(const float* mel_out, const float* post_out, const float* mel_tgt,
+                     int64_t tgt_len, const float* p_pred, const float* e_pred,
+                     const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                     const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                     int64_t batch, int64_t src_len, int64_t mel_len, int n_mel,
+                     const float* denoms, float* losses, float* ws, int64_t ws_bytes, void* stream) {
+  return loss_fwd("fs2_fs2loss_fwd", mel_out, post_out, mel_tgt, tgt_len, p_pred, e_pred, logd_pred,
+                  p_tgt, e_tgt, d_tgt, src_pad, mel_pad, batch, src_len, mel_len, n_mel, 0, 0,
+                  denoms, losses, ws, ws_bytes, stream);
+}
+
+int fs2_fs2loss_bwd(const float* mel_out, const float* post_out, const float* mel_tgt,
+                     int64_t tgt_len, const float* p_pred, const float* e_pred,
+                     const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                     const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                     int64_t batch, int64_t src_len, int64_t mel_len, int n_mel, const float* ws,
+                     const float* g_losses, float* d_mel_out, float* d_post_out, float* d_p,
+                     float* d_e, float* d_logd, void* stream) {
+  return loss_bwd("fs2_fs2loss_bwd", mel_out, post_out, mel_tgt, tgt_len, p_pred, e_pred, logd_pred,
+                  p_tgt, e_tgt, d_tgt, src_pad, mel_pad, batch, src_len, mel_len, n_mel, 0, 0, ws,
+                  g_losses, d_mel_out, d_post_out, d_p, d_e, d_logd, stream);
+}
+
+int fs2_fs2loss_level_fwd(const float* mel_out, const float* post_out, const float* mel_tgt,
+                          int64_t tgt_len, const float* p_pred, const float* e_pred,
+                          const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                          const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                          int64_t batch, int64_t src_len, int64_t mel_len, int n_mel,
+                          int p_frame, int e_frame, const float* denoms, float* losses,
+                          float* ws, int64_t ws_bytes, void* stream) {
+  return loss_fwd("fs2_fs2loss_level_fwd", mel_out, post_out, mel_tgt, tgt_len, p_pred, e_pred,
+                  logd_pred, p_tgt, e_tgt, d_tgt, src_pad, mel_pad, batch, src_len, mel_len, n_mel,
+                  p_frame != 0, e_frame != 0, denoms, losses, ws, ws_bytes, stream);
+}
+
+int fs2_fs2loss_level_bwd(const float* mel_out, const float* post_out, const float* mel_tgt,
+                          int64_t tgt_len, const float* p_pred, const float* e_pred,
+                          const float* logd_pred, const float* p_tgt, const float* e_tgt,
+                          const int64_t* d_tgt, const uint8_t* src_pad, const uint8_t* mel_pad,
+                          int64_t batch, int64_t src_len, int64_t mel_len, int n_mel,
+                          int p_frame, int e_frame, const float* ws, const float* g_losses,
+                          float* d_mel_out, float* d_post_out, float* d_p, float* d_e,
+                          float* d_logd, void* stream) {
+  return loss_bwd("fs2_fs2loss_level_bwd", mel_out, post_out, mel_tgt, tgt_len, p_pred, e_pred,
+                  logd_pred, p_tgt, e_tgt, d_tgt, src_pad, mel_pad, batch, src_len, mel_len, n_mel,
+                  p_frame != 0, e_frame != 0, ws, g_losses, d_mel_out, d_post_out, d_p, d_e, d_logd,
+                  stream);
 }
 
 int fs2_gmm_head_fwd(const float* meta, int64_t batch, int in_dim, int k, int d,

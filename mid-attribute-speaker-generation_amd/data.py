@@ -14,7 +14,8 @@ draws batches of that exact layout from a seeded generator ("SYN
 * texts on ``[1, 427]`` (0 = PAD), accents on ``[0, 3]``, speakers on ``[0, n_speakers)``,
   speaker metadata a one-hot per attribute; mels ``N(-5, 2^2)`` (log-mel range),
   pitch (f64, cast to f32 by ``to_device``) and energy (f32) ``N(0, 1)`` (already
-  z-normalised, as ``ConcatDataset`` leaves them, ``dataset.py:208-209``).
+  z-normalised, as ``ConcatDataset`` leaves them, ``dataset.py:208-209``), one value per
+  phoneme, or per mel frame for a feature asked for at ``frame_level``.
 """
 import numpy as np
 import torch
@@ -23,7 +24,12 @@ N_SYMBOLS = 428  # len(text.symbols.symbols) in the reference (text/symbols.py:2
 
 
 def syn_batch(batch_size, max_src_len=128, seed=0, frames_per_phone=4, n_speakers=209,
-              meta_sizes=(2, 2), n_mels=80):
+              meta_sizes=(2, 2), n_mels=80, pitch_level="phoneme_level",
+              energy_level="phoneme_level"):
+    """``pitch_level`` / ``energy_level`` = ``"frame_level"``: that feature is one value per mel
+    frame, ``(B, max_mel_len)`` zero-padded (``preprocessor/preprocessor.py:26-40``,
+    ``utils/tools.py:pad_1D``), drawn after every other field so the rest of the batch -- and the
+    whole default batch -- is the same for every level."""
     rng = np.random.default_rng(seed)
     B, Ts = batch_size, max_src_len
     src = np.concatenate([[Ts], rng.integers(Ts // 2, Ts + 1, size=B - 1)]).astype(np.int64)
@@ -50,6 +56,17 @@ def syn_batch(batch_size, max_src_len=128, seed=0, frames_per_phone=4, n_speaker
     speakers = rng.integers(0, n_speakers, size=B).astype(np.int64)
     meta = np.concatenate(
         [np.eye(n)[rng.integers(0, n, size=B)] for n in meta_sizes], axis=1)
+    for level in (pitch_level, energy_level):
+        if level not in ("phoneme_level", "frame_level"):
+            raise ValueError(f"feature level must be phoneme_level or frame_level, got {level!r}")
+    if pitch_level == "frame_level":
+        pitches = np.zeros((B, Tm), np.float64)
+        for b in range(B):
+            pitches[b, :int(mel[b])] = rng.standard_normal(int(mel[b]))
+    if energy_level == "frame_level":
+        energies = np.zeros((B, Tm), np.float32)
+        for b in range(B):
+            energies[b, :int(mel[b])] = rng.standard_normal(int(mel[b])).astype(np.float32)
     ids = [f"syn{seed}_{b}" for b in range(B)]
     raw = ["" for _ in range(B)]
     return (ids, raw, speakers, texts, src, int(src.max()), mels, mel.astype(np.int64),
@@ -88,23 +105,28 @@ def to_device(batch, device):
             t(accents).long().to(device))
 
 
-def pad_batch(batch, max_src_len, max_mel_len):
+def pad_batch(batch, max_src_len, max_mel_len, levels=("phoneme_level", "phoneme_level")):
     """A device batch padded on the right to ``max_src_len`` phonemes / ``max_mel_len`` frames
     (zeros, as ``collate_fn``'s ``pad_1D`` / ``pad_2D`` pad the whole batch,
     ``dataset.py:133-140``, ``utils/tools.py:329-360``); the lengths are unchanged.  Used
     for a data-parallel shard whose own maxima are below the global batch's (see
-    ``train.Trainer``)."""
+    ``train.Trainer``).  ``levels``: the (pitch, energy) feature levels; a frame-level feature
+    is padded with the mels."""
     b = list(batch)
     ds, dm = int(max_src_len) - int(b[5]), int(max_mel_len) - int(b[8])
     if ds < 0 or dm < 0:
         raise ValueError("pad_batch: target lengths below the batch's own")
     F = torch.nn.functional
+    frame = [i for i, lv in zip((9, 10), levels) if lv == "frame_level"]
     if ds:
         for i in (3, 9, 10, 11, 13):  # texts, pitches, energies, durations, accents
-            b[i] = F.pad(b[i], (0, ds))
+            if i not in frame:
+                b[i] = F.pad(b[i], (0, ds))
         b[5] = int(max_src_len)
     if dm:
         b[6] = F.pad(b[6], (0, 0, 0, dm))  # mels (B, T, n_mel)
+        for i in frame:  # a frame-level feature is (B, max_mel_len)
+            b[i] = F.pad(b[i], (0, dm))
         b[8] = int(max_mel_len)
     return tuple(b)
 

@@ -517,6 +517,44 @@ def lr_expand(x, cum, out_len, posenc=None, copy=None):
     return out, out_t
 
 
+def lr_expand_embed(x, cum, out_len, pitch=None, energy=None, posenc=None, pos_len=None,
+                    copy=None, want_pre=False, want_mid=False, want_out=True, want_idx=True):
+    """Frame-level variance adaptor in one pass (fs2_lr_expand_embed_fwd): expand ``x`` by
+    ``cum`` to ``out_len`` frames, add ``pitch`` / ``energy`` = (values (B, out_len), bins,
+    table) embeddings (None: skipped) and ``posenc`` on the first ``pos_len`` frames.  Returns
+    (pre, mid, out, out_t, p_idx, e_idx); what was not asked for is None and is not written.
+    pre / mid (the frame-level predictors' inputs) are in ``copy`` when given, else fp32."""
+    _dev(x, cum, posenc)
+    B, Ts = cum.shape
+    d = x.shape[-1]
+    rows, dev = B * out_len, x.device
+    pos_len = out_len if pos_len is None else int(pos_len)
+    if posenc is not None and posenc.numel() < pos_len * d:
+        raise RuntimeError(f"lr_expand_embed: position table shorter than {pos_len} frames")
+    args = []
+    for feat in (pitch, energy):
+        if feat is None:
+            args += [None, F32, None, 0, None]
+            continue
+        values, bins, table = feat
+        _dev(values, bins, table)
+        if values.numel() != rows or table.shape != (bins.numel() + 1, d):
+            raise RuntimeError(f"lr_expand_embed: {tuple(values.shape)} values for {B} x {out_len} "
+                               f"frames / {tuple(table.shape)} table for {bins.numel()} bins")
+        args += [ptr(values), _vals_dtype(values), ptr(bins), bins.numel(), ptr(table)]
+    cdt = torch.float32 if copy is None else copy
+    pre = torch.empty(rows, d, dtype=cdt, device=dev) if want_pre else None
+    mid = torch.empty(rows, d, dtype=cdt, device=dev) if want_mid else None
+    out = torch.empty(rows, d, dtype=torch.float32, device=dev) if want_out else None
+    out_t = _copy((rows, d), copy, dev) if want_out else None
+    p_idx = torch.empty(rows, dtype=torch.int32, device=dev) if pitch is not None and want_idx else None
+    e_idx = torch.empty(rows, dtype=torch.int32, device=dev) if energy is not None and want_idx else None
+    lib.fs2_lr_expand_embed_fwd(ptr(x), ptr(cum), B, Ts, out_len, d, *args, ptr(posenc), pos_len,
+                                code(cdt), ptr(pre), ptr(mid), ptr(out), ptr(out_t), ptr(p_idx),
+                                ptr(e_idx), stream())
+    return pre, mid, out, out_t, p_idx, e_idx
+
+
 def lr_expand_bwd(dout, cum, out_len, d):
     _dev(dout, cum)
     B, Ts = cum.shape
@@ -547,6 +585,47 @@ def fs2loss_bwd(mel_out, post_out, mel_tgt, p, e, logd, p_t, e_t, d_t, src_pad, 
     lib.fs2_fs2loss_bwd(ptr(mel_out), ptr(post_out), ptr(mel_tgt), mel_tgt.shape[1], ptr(p), ptr(e),
                         ptr(logd), ptr(p_t), ptr(e_t), ptr(d_t), ptr(src_pad), ptr(mel_pad), B, Ts,
                         Tm, n_mel, ptr(w), ptr(g6), *[ptr(o) for o in outs], stream())
+    return outs
+
+
+def _level_shapes(p, e, logd, mel_out, levels):
+    B, Tm, _ = mel_out.shape
+    Ts = logd.shape[1]
+    for name, t, frame in (("pitch", p, levels[0]), ("energy", e, levels[1])):
+        want = (B, Tm if frame else Ts)
+        if tuple(t.shape) != want:
+            raise RuntimeError(f"{'frame' if frame else 'phoneme'}-level {name} predictions are "
+                               f"{tuple(t.shape)}, the mask is {want}")
+
+
+def fs2loss_level_fwd(mel_out, post_out, mel_tgt, p, e, logd, p_t, e_t, d_t, src_pad, mel_pad,
+                      levels, denoms=None):
+    """fs2loss_fwd with ``levels = (pitch is frame-level, energy is frame-level)``: such a
+    term's predictions / targets are (B, mel_len) under ``mel_pad``."""
+    _dev(mel_out, post_out, mel_tgt, p, e, logd, p_t, e_t, d_t, src_pad, mel_pad, denoms)
+    _level_shapes(p, e, logd, mel_out, levels)
+    _level_shapes(p_t, e_t, logd, mel_out, levels)
+    B, Tm, n_mel = mel_out.shape
+    Ts = logd.shape[1]
+    losses = torch.empty(6, dtype=torch.float32, device=mel_out.device)
+    n = lib.fs2_fs2loss_ws_bytes(B, Tm)
+    w = ws(n, mel_out.device)
+    lib.fs2_fs2loss_level_fwd(ptr(mel_out), ptr(post_out), ptr(mel_tgt), mel_tgt.shape[1], ptr(p),
+                              ptr(e), ptr(logd), ptr(p_t), ptr(e_t), ptr(d_t), ptr(src_pad),
+                              ptr(mel_pad), B, Ts, Tm, n_mel, int(levels[0]), int(levels[1]),
+                              ptr(denoms), ptr(losses), ptr(w), n, stream())
+    return losses, w
+
+
+def fs2loss_level_bwd(mel_out, post_out, mel_tgt, p, e, logd, p_t, e_t, d_t, src_pad, mel_pad,
+                      levels, w, g6):
+    B, Tm, n_mel = mel_out.shape
+    Ts = logd.shape[1]
+    outs = [torch.empty_like(t) for t in (mel_out, post_out, p, e, logd)]
+    lib.fs2_fs2loss_level_bwd(ptr(mel_out), ptr(post_out), ptr(mel_tgt), mel_tgt.shape[1], ptr(p),
+                              ptr(e), ptr(logd), ptr(p_t), ptr(e_t), ptr(d_t), ptr(src_pad),
+                              ptr(mel_pad), B, Ts, Tm, n_mel, int(levels[0]), int(levels[1]),
+                              ptr(w), ptr(g6), *[ptr(o) for o in outs], stream())
     return outs
 
 

@@ -45,15 +45,62 @@ class FS2LossFn(torch.autograd.Function):
         return (d_mel, d_post, d_p, d_e, d_d) + (None,) * 8
 
 
+class FS2LevelLossFn(torch.autograd.Function):
+    """FS2LossFn with a level per variance term (fs2_fs2loss_level_*)."""
+
+    @staticmethod
+    def forward(fctx, mel_out, post_out, p, e, log_d, mels, p_t, e_t, d_t, src_pad, mel_pad, denoms,
+                g6buf, levels):
+        fctx.set_materialize_grads(False)
+        fctx.g6buf, fctx.levels = g6buf, levels
+        T = mel_out.shape[1]
+        # a frame-level target is padded to max_mel_len; the mask is the decoder's
+        crop = lambda t, frame: (t[:, :T] if frame else t).contiguous().float()
+        args = (mel_out.contiguous(), post_out.contiguous(), mels.contiguous(), p.contiguous(),
+                e.contiguous(), log_d.contiguous(), crop(p_t, levels[0]), crop(e_t, levels[1]),
+                d_t.contiguous(), src_pad.contiguous(), mel_pad[:, :T].contiguous())
+        losses, ws = K.fs2loss_level_fwd(*args, levels=levels, denoms=denoms)
+        fctx.args, fctx.ws = args, ws
+        return tuple(losses[i] for i in range(6))
+
+    @staticmethod
+    def backward(fctx, *g):
+        dev = fctx.ws.device
+        buf = fctx.g6buf
+        if g[0] is not None and all(x is None for x in g[1:]) and buf is not None:
+            buf[0:1].copy_(g[0].reshape(1))
+            g6 = buf
+        else:
+            g6 = torch.stack([x.reshape(()) if x is not None else torch.zeros((), device=dev)
+                              for x in g])
+        d_mel, d_post, d_p, d_e, d_d = K.fs2loss_level_bwd(*fctx.args, fctx.levels, fctx.ws,
+                                                           g6.float().contiguous())
+        fctx.args = fctx.g6buf = None
+        return (d_mel, d_post, d_p, d_e, d_d) + (None,) * 9
+
+
+def feature_levels(preprocess_config):
+    """(pitch is frame-level, energy is frame-level) of ``preprocess.yaml``
+    (``model/modules.py:27-34``, ``model/loss.py:10-15``)."""
+    levels = []
+    for key in ("pitch", "energy"):
+        level = preprocess_config[key]["feature"]
+        if level not in ("phoneme_level", "frame_level"):
+            raise ValueError(f"{key}.feature must be phoneme_level or frame_level, got {level!r}")
+        levels.append(level == "frame_level")
+    return tuple(levels)
+
+
 class FastSpeech2Loss(nn.Module):
-    """``model/loss.py:5-92`` (phoneme-level pitch/energy)."""
+    """``model/loss.py:5-92``: pitch and energy each phoneme-level (selected by the source
+    mask) or frame-level (selected by the mel mask, ``loss.py:51-63``)."""
 
     def __init__(self, preprocess_config, model_config):
         super().__init__()
-        for key in ("pitch", "energy"):
-            assert preprocess_config[key]["feature"] == "phoneme_level", \
-                "frame-level variance losses are not built"
-        self.denoms = None  # data-parallel: device [mel elements, phonemes] of the global batch
+        self.levels = feature_levels(preprocess_config)
+        # data-parallel: device [mel elements, phonemes] of the global batch (a frame-level
+        # term's global frame count is denoms[0] / n_mel)
+        self.denoms = None
         self._g6 = None  # persistent upstream-gradient vector (entries 1-5 stay zero)
 
     def forward(self, inputs, predictions):
@@ -61,8 +108,17 @@ class FastSpeech2Loss(nn.Module):
         (mel_out, post_out, p, e, log_d, _, src_masks, mel_masks, _, _) = predictions[:10]
         if self._g6 is None or self._g6.device != mel_out.device:
             self._g6 = torch.zeros(6, dtype=torch.float32, device=mel_out.device)
-        return FS2LossFn.apply(mel_out, post_out, p, e, log_d, mels, p_t, e_t, d_t, src_masks,
-                               mel_masks, self.denoms, self._g6)
+        if not any(self.levels):
+            return FS2LossFn.apply(mel_out, post_out, p, e, log_d, mels, p_t, e_t, d_t, src_masks,
+                                   mel_masks, self.denoms, self._g6)
+        for name, pred, frame in (("pitch", p, self.levels[0]), ("energy", e, self.levels[1])):
+            if frame and pred.shape[1] != mel_masks.shape[1]:
+                raise ValueError(
+                    f"frame-level {name} predictions have {pred.shape[1]} frames but the decoder "
+                    f"mask {mel_masks.shape[1]}: the reference's masked_select (model/loss.py:55-56, "
+                    "62-63) fails on a decoder truncated to max_seq_len (transformer/Models.py:166-173)")
+        return FS2LevelLossFn.apply(mel_out, post_out, p, e, log_d, mels, p_t, e_t, d_t, src_masks,
+                                    mel_masks, self.denoms, self._g6, self.levels)
 
 
 class GMMMeanLogProbFn(torch.autograd.Function):

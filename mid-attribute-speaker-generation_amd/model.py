@@ -841,15 +841,17 @@ class VariancePredictor(nn.Module):
 
 
 class VarianceAdaptor(nn.Module):
-    """``model/modules.py:17-158`` (phoneme-level pitch and energy, linear bins)."""
+    """``model/modules.py:17-158`` (pitch and energy each phoneme- or frame-level, linear
+    bins).  ``pitch_frame`` / ``energy_frame``: that feature is predicted and embedded after
+    the LengthRegulator (``modules.py:139-148``)."""
 
     def __init__(self, preprocess_config, model_config, config_path):
         super().__init__()
+        from .loss import feature_levels
         d = model_config["transformer"]["encoder_hidden"]
         n_bins = model_config["variance_embedding"]["n_bins"]
+        self.pitch_frame, self.energy_frame = feature_levels(preprocess_config)
         for key in ("pitch", "energy"):
-            assert preprocess_config[key]["feature"] == "phoneme_level", \
-                "frame-level variance features are not built (SURVEY.md §8a row 10)"
             assert model_config["variance_embedding"][f"{key}_quantization"] == "linear", \
                 "log quantisation is not built"
         p_min, p_max, e_min, e_max = cfg.pitch_energy_range(config_path)
@@ -1201,6 +1203,136 @@ class VarianceAdaptorFn(torch.autograd.Function):
         return (None, dx) + (None,) * 10
 
 
+# One launch for "expand + frame-level embeddings + position encoding" (fs2_lr_expand_embed_fwd);
+# False: the four-launch composition it is bitwise equal to (A/B, profiles/frame_level_expand_ab.txt)
+FUSE_FRAME_EXPAND = True
+
+
+def _frame_expand(x, cum, T, pitch, energy, posenc, T_pos, copy, want_pre, want_mid, fused=None,
+                  pos_tiled=None):
+    """(pre, mid, out, out_t, p_idx, e_idx) of ``K.lr_expand_embed`` -- by that one launch, or
+    composed from lr_expand -> bucket_embed -> bucket_embed -> + posenc[:T_pos] per utterance
+    (bitwise the same; pre / mid are then the compute copies of the composition's fp32
+    intermediates; ``pos_tiled``: the (B * T, d) position rows, for one add when T_pos == T)."""
+    if FUSE_FRAME_EXPAND if fused is None else fused:
+        return K.lr_expand_embed(x, cum, T, pitch=pitch, energy=energy, posenc=posenc,
+                                 pos_len=T_pos, copy=copy, want_pre=want_pre, want_mid=want_mid)
+    B, d = cum.shape[0], x.shape[-1]
+    last = "energy" if energy is not None else ("pitch" if pitch is not None else "expand")
+    v, v_t = K.lr_expand(x, cum, T, copy=copy if want_pre else None)
+    pre = _t(v, v_t) if want_pre else None
+    mid = p_idx = e_idx = None
+    if pitch is not None:
+        v, v_t, p_idx = K.bucket_embed(v, pitch[0].contiguous().view(-1), pitch[1], pitch[2],
+                                       copy=copy if want_mid else None)
+        mid = _t(v, v_t) if want_mid else None
+    if energy is not None:
+        v, _, e_idx = K.bucket_embed(v, energy[0].contiguous().view(-1), energy[1], energy[2])
+    if (last == "expand" and want_pre) or (last == "pitch" and want_mid):
+        v = v.clone()  # the predictor's fp32 input must not receive the position encoding
+    rows = v.view(B, T, d)
+    pos = posenc.reshape(-1, d)[:T_pos]
+    if pos_tiled is not None and T_pos == T:
+        K.add(v, pos_tiled, out=v)
+    else:
+        for b in range(B):
+            K.add(rows[b, :T_pos], pos, out=rows[b, :T_pos])
+    return pre, mid, v, (K.cast_bf16(v) if copy is not None else None), p_idx, e_idx
+
+
+class VarianceAdaptorFrameFn(torch.autograd.Function):
+    """Speaker add + variance adaptor (training branch) + decoder position encoding with pitch
+    and / or energy at frame level (``model/modules.py:116-148``).  A phoneme-level feature is
+    predicted and embedded before the LengthRegulator as in VarianceAdaptorFn; a frame-level
+    one after it, on (B, T_mel) rows under the mel mask, its embedding added at every frame
+    (padded frames hold ``table[bucketize(0)]``: the targets are zero-padded)."""
+
+    @staticmethod
+    def forward(fctx, token, enc_out, m, speakers, src_lens, mel_lens, p_t, e_t, d_t, B, Ts, T,
+                ctx):
+        fctx.set_materialize_grads(False)
+        va = m.variance_adaptor
+        pf, ef = va.pitch_frame, va.energy_frame
+        x, x_t = K.rowvec_add(enc_out, speakers, m.speaker_emb.weight, B, Ts, copy=ctx.copy)
+        # the phoneme-level predictors read x0 only: on the side stream, as in VarianceAdaptorFn
+        side = ctx.side.cuda_stream if ctx.side is not None and VA_SIDE else None
+        if side is not None:
+            K.lib.fs2_stream_wait(side, K.stream())
+        log_d, s_d = va.duration_predictor.fwd(x, x_t, src_lens, B, Ts, ctx, stream=side)
+        idx_p = idx_e = p = e = None
+        if not pf:  # modules.py:117-121
+            p, s_p = va.pitch_predictor.fwd(x, x_t, src_lens, B, Ts, ctx, stream=side)
+            x, _, idx_p = K.bucket_embed(x, p_t.contiguous().view(-1), va.pitch_bins,
+                                         va.pitch_embedding.weight)
+        if not ef:  # modules.py:122-126: reads x0 when the pitch is frame-level
+            e, s_e = va.energy_predictor.fwd(x, x_t, src_lens, B, Ts, ctx, stream=side)
+            x, _, idx_e = K.bucket_embed(x, e_t.contiguous().view(-1), va.energy_bins,
+                                         va.energy_embedding.weight)
+        cum, mel_len = K.lr_index(d_t.contiguous())
+        pre, mid, x_lr, x_lr_t, fp, fe = _frame_expand(
+            x, cum, T,
+            (p_t.contiguous(), va.pitch_bins, va.pitch_embedding.weight) if pf else None,
+            (e_t.contiguous(), va.energy_bins, va.energy_embedding.weight) if ef else None,
+            m.decoder.position_enc, T, ctx.copy, True, pf and ef)
+        if pf:  # modules.py:139-143
+            idx_p = fp
+            p, s_p = va.pitch_predictor.fwd(pre, pre if ctx.copy is not None else None, mel_lens,
+                                            B, T, ctx)
+        if ef:  # modules.py:144-148: after the pitch embedding when both are frame-level
+            idx_e = fe
+            xe = mid if pf else pre
+            e, s_e = va.energy_predictor.fwd(xe, xe if ctx.copy is not None else None, mel_lens,
+                                             B, T, ctx)
+        if side is not None:
+            K.lib.fs2_stream_wait(K.stream(), side)
+        fctx.m, fctx.saved = m, (s_d, s_p, s_e, idx_p, idx_e, cum, speakers, B, Ts, T, ctx)
+        side = x_lr_t if x_lr_t is not None else torch.empty(0, device=x_lr.device)
+        fctx.mark_non_differentiable(mel_len, side)
+        return x_lr, log_d, p, e, mel_len, side
+
+    @staticmethod
+    def backward(fctx, d_xlr, d_logd, d_p, d_e, _a, _b):
+        m = fctx.m
+        va = m.variance_adaptor
+        pf, ef = va.pitch_frame, va.energy_frame
+        s_d, s_p, s_e, idx_p, idx_e, cum, speakers, B, Ts, T, ctx = fctx.saved
+        d = m.encoder.d
+        dev = m._token.device
+
+        def energy(dx):
+            K.bucket_embed_bwd(dx, idx_e, _g(va.energy_embedding.weight))
+            if d_e is not None:
+                va.energy_predictor.bwd(d_e, s_e, dx)
+            ctx.notify(lambda: [va.energy_embedding.weight] + vp_param_order(va.energy_predictor))
+
+        def pitch(dx):
+            K.bucket_embed_bwd(dx, idx_p, _g(va.pitch_embedding.weight))
+            if d_p is not None:
+                va.pitch_predictor.bwd(d_p, s_p, dx)
+            ctx.notify(lambda: [va.pitch_embedding.weight] + vp_param_order(va.pitch_predictor))
+
+        # the reverse of the forward's order: each table's gradient is reduced from a dx that
+        # already holds every later consumer's input gradient (fixed order, no atomics).  The
+        # decoder's input gradient is this step's own fresh tensor: accumulated into in place
+        dxf = K.zeros((B * T, d), dev) if d_xlr is None else d_xlr.contiguous()
+        if ef:
+            energy(dxf)
+        if pf:
+            pitch(dxf)
+        dx = K.lr_expand_bwd(dxf, cum, T, d)
+        if not ef:
+            energy(dx)
+        if not pf:
+            pitch(dx)
+        if d_logd is not None:
+            va.duration_predictor.bwd(d_logd, s_d, dx)
+        ctx.notify(lambda: vp_param_order(va.duration_predictor))
+        K.rowvec_add_bwd(dx, speakers, _g(m.speaker_emb.weight), B, Ts)
+        ctx.notify(lambda: [m.speaker_emb.weight])
+        fctx.saved = None
+        return (None, dx) + (None,) * 11
+
+
 class DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, token, x, x_t, dec, lens, B, T, ctx):
@@ -1477,6 +1609,7 @@ class FastSpeech2(nn.Module):
             return self._forward_infer(speakers, texts, src_lens, max_src_len, mel_lens,
                                        max_mel_len, p_targets, e_targets, d_targets, p_control,
                                        e_control, d_control, accents, speaker_meta=speaker_meta)
+        self._check_frame_level(int(max_mel_len), p_targets, e_targets, truncates=True)
         self.arena()
         side = self.side_stream() if self.training else None
         after_first = self.prep_weights(side)
@@ -1503,13 +1636,40 @@ class FastSpeech2(nn.Module):
         gmm = self.speaker_enc(speaker_meta)
         if side is not None:  # the weights prepared on the side stream (prep_weights)
             K.lib.fs2_stream_wait(K.stream(), side.cuda_stream)
-        x_lr, log_d, p, e, mel_len, x_lr_t = VarianceAdaptorFn.apply(
-            tok, enc, self, speakers.contiguous(), src_lens, p_targets, e_targets, d_targets, B, Ts,
-            T_dec, ctx)
+        va = self.variance_adaptor
+        if va.pitch_frame or va.energy_frame:
+            x_lr, log_d, p, e, mel_len, x_lr_t = VarianceAdaptorFrameFn.apply(
+                tok, enc, self, speakers.contiguous(), src_lens, mel_lens, p_targets, e_targets,
+                d_targets, B, Ts, T_dec, ctx)
+        else:
+            x_lr, log_d, p, e, mel_len, x_lr_t = VarianceAdaptorFn.apply(
+                tok, enc, self, speakers.contiguous(), src_lens, p_targets, e_targets, d_targets,
+                B, Ts, T_dec, ctx)
         x, x_t = DecoderFn.apply(tok, x_lr, x_lr_t, self.decoder, mel_lens, B, T_dec, ctx)
         output, postnet_output = MelHeadFn.apply(tok, x, x_t, self, B, T_dec, ctx)
         return (output, postnet_output, p, e, log_d, d_targets, src_masks, mel_masks, src_lens,
                 mel_len, gmm, speaker_emb_s)
+
+    def _check_frame_level(self, max_mel_len, p_targets, e_targets, truncates):
+        """Frame-level targets are (B, max_mel_len) (``dataset.py`` loads the per-frame arrays,
+        ``pad_1D`` pads them).  ``truncates``: the training-mode decoder cuts its mask to
+        ``max_seq_len`` while the frame-level predictions keep ``max_mel_len`` columns, which the
+        reference cannot train on."""
+        va = self.variance_adaptor
+        if not (va.pitch_frame or va.energy_frame):
+            return
+        if truncates and max_mel_len > self.decoder.max_seq_len:
+            raise ValueError(
+                f"frame-level pitch/energy with max_mel_len {max_mel_len} > max_seq_len "
+                f"{self.decoder.max_seq_len} in training mode: the decoder returns a mel mask "
+                "truncated to max_seq_len (transformer/Models.py:166-173) while the frame-level "
+                "predictions keep max_mel_len columns, so the reference's masked_select "
+                "(model/loss.py:55-56, 62-63) fails; shorten the batch or raise max_seq_len")
+        for name, t, frame in (("pitch", p_targets, va.pitch_frame),
+                               ("energy", e_targets, va.energy_frame)):
+            if frame and t is not None and t.shape[1] != max_mel_len:
+                raise ValueError(f"frame-level {name} targets have {t.shape[1]} columns, "
+                                 f"max_mel_len is {max_mel_len}")
 
     # -- inference ----------------------------------------------------------------------
     def _posenc(self, T):
@@ -1525,6 +1685,38 @@ class FastSpeech2(nn.Module):
             cache[n] = sinusoid_table(n, self.decoder.d).to(tab.device)[None]
         return cache[n]
 
+    def _frame_level_infer(self, x2, cum, lens, B, T, T_dec, p, e, p_targets, e_targets, values,
+                           ctx):
+        """The frame-level features of ``modules.py:139-148`` without autograd: one
+        fs2_lr_expand_embed_fwd launch per stage, each re-expanding the (small) phoneme rows
+        ``x2`` and adding what is known so far in the reference's order -- the pitch predictor
+        reads the expanded rows, the energy predictor those plus the pitch embedding (the
+        energy embedding depends on its own prediction), and the last launch writes the decoder
+        input with the position table on the first ``T_dec`` of the ``T`` frames.  Returns
+        (decoder input, its compute copy, p, e)."""
+        va = self.variance_adaptor
+        self._check_frame_level(T, p_targets, e_targets, truncates=False)
+        stage = dict(copy=ctx.copy, want_out=False, want_idx=False)
+        cpy = lambda t: t if ctx.copy is not None else None
+        pitch = energy = None
+        if va.pitch_frame:
+            pre = K.lr_expand_embed(x2, cum, T, want_pre=True, **stage)[0]
+            p, _ = va.pitch_predictor.fwd(pre, cpy(pre), lens, B, T, ctx)
+            pitch = (values(p, p_targets), va.pitch_bins, va.pitch_embedding.weight)
+        if va.energy_frame:
+            xe = K.lr_expand_embed(x2, cum, T, pitch=pitch, want_pre=pitch is None,
+                                   want_mid=pitch is not None, **stage)[0 if pitch is None else 1]
+            e, _ = va.energy_predictor.fwd(xe, cpy(xe), lens, B, T, ctx)
+            energy = (values(e, e_targets), va.energy_bins, va.energy_embedding.weight)
+        _, _, x, x_t, _, _ = K.lr_expand_embed(x2, cum, T, pitch=pitch, energy=energy,
+                                               posenc=self._posenc(T_dec), pos_len=T_dec,
+                                               copy=ctx.copy, want_idx=False)
+        if T_dec < T:  # training-mode truncation (Models.py:166-173): the decoder's frames only
+            d = x.shape[1]
+            x = x.view(B, T, d)[:, :T_dec].reshape(B * T_dec, d)
+            x_t = None if x_t is None else x_t.view(B, T, d)[:, :T_dec].reshape(B * T_dec, d)
+        return x, x_t, p, e
+
     def _forward_infer(self, speakers, texts, src_lens, max_src_len, mel_lens, max_mel_len,
                        p_targets, e_targets, d_targets, p_control, e_control, d_control, accents,
                        speaker_meta=None, speaker_vec=None):
@@ -1533,7 +1725,8 @@ class FastSpeech2(nn.Module):
 
         * pitch / energy without a target: prediction * control, bucketized
           (``modules.py:80-100``); energy uses ``p_control`` (``modules.py:124``, quirk kept,
-          so ``e_control`` is accepted and unused as in the reference);
+          so ``e_control`` is accepted and unused as in the reference); a frame-level feature
+          is predicted and embedded after the LengthRegulator (``_frame_level_infer``);
         * durations without a target: ``fs2_duration_round`` then the LengthRegulator; the
           frame count max(mel_len) is the one device->host read (``utils/tools.py:157``);
         * eval-mode decoder past ``max_seq_len``: no truncation, fresh position table
@@ -1568,24 +1761,28 @@ class FastSpeech2(nn.Module):
             gmm = self.speaker_enc(speaker_meta) if speaker_meta is not None else None
             x0, x0_t = K.rowvec_add(x, ids, table, B, Ts, copy=ctx.copy)
             log_d, _ = va.duration_predictor.fwd(x0, x0_t, src_lens, B, Ts, ctx)
-            p, _ = va.pitch_predictor.fwd(x0, x0_t, src_lens, B, Ts, ctx)
-            if p_targets is None:
+            pf, ef = va.pitch_frame, va.energy_frame
+
+            def values(pred, target):
+                # modules.py:82-88 / 93-99: the target, or prediction * control (p_control for
+                # the energy too, modules.py:124,146)
+                if target is not None:
+                    return target.contiguous()
                 if p_control != 1.0:
-                    K.scale_(p, p_control)
-                p_vals = p
-            else:
-                p_vals = p_targets
-            x1, x1_t, _ = K.bucket_embed(x0, p_vals.contiguous().view(-1), va.pitch_bins,
-                                         va.pitch_embedding.weight, copy=ctx.copy)
-            e, _ = va.energy_predictor.fwd(x1, x1_t, src_lens, B, Ts, ctx)
-            if e_targets is None:
-                if p_control != 1.0:
-                    K.scale_(e, p_control)
-                e_vals = e
-            else:
-                e_vals = e_targets
-            x2, _, _ = K.bucket_embed(x1, e_vals.contiguous().view(-1), va.energy_bins,
-                                      va.energy_embedding.weight)
+                    K.scale_(pred, p_control)
+                return pred
+
+            x2, x2_t = x0, x0_t
+            p = e = None
+            if not pf:
+                p, _ = va.pitch_predictor.fwd(x0, x0_t, src_lens, B, Ts, ctx)
+                x2, x2_t, _ = K.bucket_embed(x0, values(p, p_targets).view(-1), va.pitch_bins,
+                                             va.pitch_embedding.weight,
+                                             copy=None if ef else ctx.copy)
+            if not ef:  # reads x0 when the pitch is frame-level (modules.py:122-126)
+                e, _ = va.energy_predictor.fwd(x2, x2_t, src_lens, B, Ts, ctx)
+                x2, _, _ = K.bucket_embed(x2, values(e, e_targets).view(-1), va.energy_bins,
+                                          va.energy_embedding.weight)
             if d_targets is not None:
                 if mel_lens is None:
                     raise ValueError("d_targets without mel_lens: the decoder has no mask "
@@ -1605,7 +1802,11 @@ class FastSpeech2(nn.Module):
                                      "the reference's decoder mask would not broadcast")
             T_dec = T if (not self.training and T > dec.max_seq_len) else min(T, dec.max_seq_len)
             mel_masks = K.length_mask(dec_lens, T_dec)
-            x, x_t = K.lr_expand(x2, cum, T_dec, posenc=self._posenc(T_dec), copy=ctx.copy)
+            if pf or ef:
+                x, x_t, p, e = self._frame_level_infer(x2, cum, dec_lens, B, T, T_dec, p, e,
+                                                       p_targets, e_targets, values, ctx)
+            else:
+                x, x_t = K.lr_expand(x2, cum, T_dec, posenc=self._posenc(T_dec), copy=ctx.copy)
             for layer in dec.layer_stack:
                 x, x_t, _ = layer.fwd(x, x_t, dec_lens, B, T_dec, ctx)
             lin = self.mel_linear

@@ -367,7 +367,10 @@ class Trainer:
         if ts == int(batch[5]) and tm == int(batch[8]):
             return batch
         from .data import pad_batch
-        return pad_batch(batch, ts, tm)
+        loss = getattr(self, "Loss", None)  # a frame-level feature is padded with the mels
+        levels = tuple("frame_level" if f else "phoneme_level"
+                       for f in (loss.levels if loss is not None else (False, False)))
+        return pad_batch(batch, ts, tm, levels)
 
     def _global_denominators(self, batch):
         T_dec = min(int(batch[8]), self.model.decoder.max_seq_len)
