@@ -177,7 +177,8 @@ int fs2_lstm_layer_fwd(const float* x, int64_t n_seq, int64_t steps, int64_t c_i
  * writes dgates (rows, 4H; pre-activation gate gradients) and, when dx is given,
  * dx = dgates W_ih (rows, c_in; w_ih_t = W_ih^T (c_in, 4H)); w_hh_t = W_hh^T (H, 4H).
  * dc_ws: 2*n_seq*H floats.
- * Weight gradients are not formed (train.py never steps the discriminator).            */
+ * The weight gradients are a separate entry (fs2_lstm_stack_wgrad, from dgates and h):
+ * train.py never steps the discriminator, so its path does not pay for them.           */
 int fs2_lstm_layer_bwd(const float* dh_out, int64_t n_seq, int64_t steps, int64_t c_in,
                        int64_t hidden, const float* w_ih_t, const float* w_hh_t, const float* act,
                        const float* c_all, float* dgates, float* dc_ws, float* dx, void* stream);
@@ -199,6 +200,21 @@ int fs2_lstm_stack_bwd(const float* dh_out, int64_t n_seq, int64_t steps, int64_
                        int64_t hidden, int layers, const float* w_ih0_t, const float* w_ih_up_t,
                        const float* w_hh_t, const float* act, const float* c_all, float* dgates,
                        float* dc_ws, float* dx, void* stream);
+/* Weight gradients of the stack (train_speech_embedder.py), from what the forward and the
+ * backward left: x (rows, c_in), h_all (L, rows, H), dgates (L, rows, 4H).  Per layer
+ *   dW_ih (4H, c_in_l) = sum_rows dgates^T (x) in_l,   in_0 = x, in_l = h[l-1]
+ *   dW_hh (4H, H)      = sum_rows dgates^T (x) h[l][row-1]  (0 at the first step of a sequence)
+ *   db    (4H)         = sum_rows dgates     (the gradient of b_ih and of b_hh alike)
+ * in the stack's weight layout: dw_ih0 (4H, c_in), dw_ih_up (L-1, 4H, H), dw_hh (L, 4H, H),
+ * db (L, 4H).  f32 MFMA; the rows are split over blocks and the slices added in a fixed order,
+ * so the result is bitwise repeatable.  beta = 0 overwrites the outputs, beta = 1 adds to them.
+ * hidden a multiple of 256, c_in of 4, n_seq, steps >= 1; ws: fs2_lstm_stack_wgrad_ws_bytes. */
+int64_t fs2_lstm_stack_wgrad_ws_bytes(int64_t n_seq, int64_t steps, int64_t c_in, int64_t hidden,
+                                      int layers);
+int fs2_lstm_stack_wgrad(const float* x, const float* h_all, const float* dgates, int64_t n_seq,
+                         int64_t steps, int64_t c_in, int64_t hidden, int layers, float* dw_ih0,
+                         float* dw_ih_up, float* dw_hh, float* db, int beta, float* ws,
+                         int64_t ws_bytes, void* stream);
 /* Embedding + domain-classifier head on the last LSTM frame (x row n at x + n*ldx, 256 wide):
  * projection 256->64, L2 norm (emb), Linear 64->64, dropout, ReLU, Linear 64->64, dropout,
  * ReLU, Linear 64->1 (logit).  w*t are the transposed weights (forward), w* the natural
@@ -210,6 +226,27 @@ int fs2_clf_head(const float* x, int64_t ldx, int64_t n, const float* wp, const 
                  const float* b2, float p_drop, const uint64_t* seed, uint64_t site, float* emb,
                  float* logit, const float* demb, const float* dlogit, float* dx, int64_t lddx,
                  void* stream);
+/* Weight gradients of that head for the given demb / dlogit (NULL = 0): projection dwp (64, 256),
+ * dbp (64); classifier dw0, dw1 (64, 64), db0, db1 (64), dw2 (1, 64), db2 (1).  Same weight
+ * operands and regenerated dropout masks as fs2_clf_head; rows added in row order; beta = 0
+ * overwrites, beta = 1 adds.  ws: fs2_clf_head_wgrad_ws_bytes(n).                         */
+int64_t fs2_clf_head_wgrad_ws_bytes(int64_t n);
+int fs2_clf_head_wgrad(const float* x, int64_t ldx, int64_t n, const float* wp, const float* wpt,
+                       const float* bp, const float* w0, const float* w0t, const float* b0,
+                       const float* w1, const float* w1t, const float* b1, const float* w2,
+                       const float* b2, float p_drop, const uint64_t* seed, uint64_t site,
+                       const float* demb, const float* dlogit, float* dwp, float* dbp, float* dw0,
+                       float* db0, float* dw1, float* db1, float* dw2, float* db2, int beta,
+                       float* ws, int64_t ws_bytes, void* stream);
+/* GE2E softmax loss of emb (n_spk, m_utt >= 2, dim <= 256) (utils.py:77-90, 126-135,
+ * speech_embedder_net.py:173-181): S_jik = w cos(e_ji, c_k) + b, c_k the mean over m_utt, the
+ * k = j entry against the exclude-self centroid; loss = sum_ji log(sum_k exp S_jik + 1e-6) -
+ * S_jij.  w, b, g device scalars (g = upstream gradient, NULL = 1).  loss, and with demb also
+ * demb (n_spk, m_utt, dim), dw, db (each nullable).  ws: fs2_ge2e_softmax_ws_bytes.       */
+int64_t fs2_ge2e_softmax_ws_bytes(int64_t n_spk, int64_t m_utt, int64_t dim);
+int fs2_ge2e_softmax(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim, const float* w,
+                     const float* b, const float* g, float* loss, float* demb, float* dw,
+                     float* db, float* ws, int64_t ws_bytes, void* stream);
 /* BCEWithLogits per row (loss_rows, nullable) and dlogit = g[0] * scale * (sigmoid - y)
  * (g nullable = 1).                                                                      */
 int fs2_bce_logits(const float* logit, const float* y, int64_t n, float* loss_rows,
@@ -711,6 +748,16 @@ int fs2_grad_norm(const float* g, int64_t n, float max_norm, float* norm_coef, f
 int fs2_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* norm_coef,
                   float lr, float beta1, float beta2, float eps, float bias_corr1,
                   float bias_corr2_sqrt, const float* hyper, void* stream);
+/* torch.optim.Adam with coupled L2 weight decay (train_speech_embedder.py:104-113):
+ * g <- norm_coef[1] g + weight_decay p (clip first), then Adam.  step (device int64[1]) is the
+ * optimiser's step count, hyper (device float[3]) scratch.  gate (device float, nullable):
+ * with gate[0] == 0 nothing changes, step included -- torch's "no parameter has a gradient". */
+int fs2_adam_l2_step(float* p, const float* g, float* m, float* v, int64_t n,
+                     const float* norm_coef, float lr, float beta1, float beta2, float eps,
+                     float weight_decay, int64_t* step, float* hyper, const float* gate,
+                     void* stream);
+/* out[0] = x[0] < threshold ? 1 : 0 (a device-side condition for the gates above)      */
+int fs2_gate_lt(const float* x, float threshold, float* out, void* stream);
 /* Device-side ScheduledOptim.step_and_update_lr (model/optimizer.py:33-51): steps (device,
  * int64[2] = [current_step, adam t]) are incremented (current_step only when advance_lr;
  * step() without the LR update passes 0) and hyper (device, float[3]) set to

@@ -13,16 +13,20 @@ Mirrors ``Multilingual-Speaker-Encoder-with-Domain-Adaptation/speech_embedder_ne
   (``speech_embedder_net.py:165-186``).  ``train.py:190`` only back-propagates ``da_loss``;
   the GE2E similarity term there has M = 1 utterance per "speaker", for which the
   reference's exclude-self centroid divides by M - 1 = 0 (``utils.py:36``) -- it is NaN and
-  returned as NaN here as well (M > 1, the speaker-encoder pre-training loss, is outside
-  the hot path and raises).
+  returned as NaN here as well.  For M > 1, the speaker-encoder training loss, the softmax
+  GE2E loss is one kernel forward and one backward (``fs2_ge2e_softmax``); the 'contrast'
+  variant is not built and raises.
 
 Kernels (``csrc/lstm.hip``): the 3-layer stack runs as a wavefront -- launch s computes
 layer l at step s - l, all layers in one launch (T + 2 launches instead of 3T), with the
 inputs of layers 1-2 folded into their step kernels; layer 0's input projection is one GEMM.
 The backward is the same in reverse plus one GEMM for the input gradient.  The head (projection .. logit) is one kernel,
-one wave per sequence, forward and backward.  The discriminator's own weight gradients are
-not formed: ``train.py`` never steps it (its parameters are set ``requires_grad`` but no
-optimiser holds them), so only the gradient into FastSpeech2's mel output is computed.
+one wave per sequence, forward and backward.  ``train.py`` never steps the discriminator (its
+parameters are set ``requires_grad`` but no optimiser holds them), so by default only the
+gradient into FastSpeech2's mel output is computed.  ``SpeechEmbedder(weight_grads=True)``
+also forms the discriminator's own weight gradients, for ``embedder_train.EmbedderTrainer``:
+the LSTM's from the saved ``h`` and the backward's ``dgates`` in one split-row f32-MFMA GEMM
+per layer (``csrc/lstm_wgrad.hip``), the head's in ``fs2_clf_head_wgrad``.
 """
 import math
 
@@ -42,7 +46,7 @@ def _p(t):
 
 class _EmbedderFn(torch.autograd.Function):
     @staticmethod
-    def forward(fctx, x, emb_mod, seed):
+    def forward(fctx, x, emb_mod, seed, detach, anchor):
         N, T, D = x.shape
         dev = x.device
         w = emb_mod._prep()
@@ -66,6 +70,9 @@ class _EmbedderFn(torch.autograd.Function):
                          emb_mod.site, _p(emb), _p(logit), None, None, None, 0, K.stream())
         fctx.emb_mod, fctx.saved, fctx.h_top, fctx.seed = emb_mod, saved, inp, seed
         fctx.shape, fctx.p = (N, T, D), p
+        # weight gradients (train_speech_embedder.py): the backward also needs x and every
+        # layer's h; detach = the reference's detach=True (classifier gradients only)
+        fctx.wgrad = (xc, h, detach) if emb_mod.weight_grads else None
         return emb, logit
 
     @staticmethod
@@ -73,11 +80,16 @@ class _EmbedderFn(torch.autograd.Function):
         N, T, D = fctx.shape
         dev = fctx.h_top.device
         w = fctx.emb_mod._prep()
-        dh = K.zeros((N * T, HIDDEN), dev)
         last_in = _p(fctx.h_top) + (T - 1) * HIDDEN * 4
-        last_out = _p(dh) + (T - 1) * HIDDEN * 4
         demb = demb.contiguous() if demb is not None else None
         dlogit = dlogit.contiguous() if dlogit is not None else None
+        if fctx.wgrad is not None:
+            fctx.emb_mod._head_wgrad(last_in, T * HIDDEN, N, w, fctx.p, fctx.seed, demb, dlogit,
+                                     fctx.wgrad[2])
+            if fctx.wgrad[2]:  # detached embedding: nothing reaches the LSTM
+                return None, None, None, None, None
+        dh = K.zeros((N * T, HIDDEN), dev)
+        last_out = _p(dh) + (T - 1) * HIDDEN * 4
         lib.fs2_clf_head(last_in, T * HIDDEN, N, *w["head"], fctx.p,
                          _p(fctx.seed) if fctx.p > 0 else None, fctx.emb_mod.site, None, None,
                          _p(demb) if demb is not None else None,
@@ -87,12 +99,14 @@ class _EmbedderFn(torch.autograd.Function):
         st = w["stack"]
         dgates = torch.empty(LAYERS, N * T, 4 * HIDDEN, device=dev)
         dc = torch.empty(LAYERS * 2 * N * HIDDEN, device=dev)
-        dx = torch.empty(N * T, D, device=dev)
+        dx = torch.empty(N * T, D, device=dev) if fctx.needs_input_grad[0] else None
         lib.fs2_lstm_stack_bwd(_p(dh), N, T, D, HIDDEN, LAYERS, _p(st["w_ih0_t"]),
                                _p(st["w_ih_up_t"]), _p(st["w_hh_t"]), _p(act), _p(c), _p(dgates),
-                               _p(dc), _p(dx), K.stream())
+                               _p(dc), K.ptr(dx), K.stream())
+        if fctx.wgrad is not None:
+            fctx.emb_mod._lstm_wgrad(fctx.wgrad[0], fctx.wgrad[1], dgates, N, T)
         dh = dx
-        return dh.view(N, T, D), None, None
+        return (dh.view(N, T, D) if dh is not None else None), None, None, None, None
 
 
 class _Module(nn.Module):
@@ -106,10 +120,16 @@ def _linear_norm(in_dim, out_dim, dev):
 
 
 class SpeechEmbedder(nn.Module):
-    """``speech_embedder_net.py:65-146`` (LSTM architecture, language DA head)."""
+    """``speech_embedder_net.py:65-146`` (LSTM architecture, language DA head).
 
-    def __init__(self, device="cuda"):
+    ``weight_grads=False`` is the ``--use_clf`` discriminator: the backward gives the input
+    gradient only and no parameter gets a ``.grad``.  With ``True`` the backward also
+    accumulates every parameter's gradient into ``.grad`` (``embedder_train.EmbedderTrainer``),
+    and ``forward(x, detach=True)`` back-propagates into the classifier alone."""
+
+    def __init__(self, device="cuda", weight_grads=False):
         super().__init__()
+        self.weight_grads = bool(weight_grads)
         dev = torch.device(device)
         self.LSTM_stack = nn.LSTM(NMELS, HIDDEN, num_layers=LAYERS, batch_first=True, device=dev)
         self.projection = _linear_norm(HIDDEN, PROJ, dev)
@@ -179,10 +199,74 @@ class SpeechEmbedder(nn.Module):
         if self.training and self.da_dropout > 0:
             K.seed_next(self._seed_state)  # a fresh classifier dropout key per call
         seed = self._seed_state[2:3].clone()  # this call's key (the backward re-reads it)
-        emb, logit = _EmbedderFn.apply(x.float(), self, seed)
+        if self.weight_grads:
+            # the parameters are not inputs of the function (their gradients are accumulated
+            # by hand); one of them rides along so that autograd runs the backward
+            emb, logit = _EmbedderFn.apply(x.float(), self, seed, bool(detach),
+                                           self.projection.linear_layer.bias)
+        else:
+            emb, logit = _EmbedderFn.apply(x.float(), self, seed, False, None)
         if detach:
             emb = emb.detach()
         return {"embeddings": emb, "da_lang_logits": logit}
+
+    # -- speech_embedder_net.py:97-118 -------------------------------------------------------
+    def _head_layers(self):
+        return [self.projection.linear_layer] + [
+            getattr(self.da_classifier.classifier.layer, f"linear_{i}").linear_layer
+            for i in range(3)]
+
+    def da_parameters(self):
+        return list(self.da_classifier.parameters())
+
+    def main_parameters(self):
+        return list(self.LSTM_stack.parameters()) + list(self.projection.parameters())
+
+    def compute_embedding(self, x):
+        """``{'embeddings': (N, 64)}`` without the classifier's output."""
+        return {"embeddings": self.forward(x)["embeddings"]}
+
+    # -- weight gradients (weight_grads=True) ----------------------------------------------
+    @staticmethod
+    def _acc(p, g):
+        """p.grad += g, like autograd's accumulation (p.grad may be a view of a flat arena)."""
+        if p.grad is None:
+            p.grad = K.zeros(p.shape, g.device)
+        K.add(p.grad, g, out=p.grad)
+
+    def _head_wgrad(self, last, ldx, n, w, p, seed, demb, dlogit, detach):
+        dev = seed.device
+        sizes = [PROJ * HIDDEN, PROJ, PROJ * PROJ, PROJ, PROJ * PROJ, PROJ, PROJ, 1]
+        buf = torch.empty(sum((s + 3) // 4 * 4 for s in sizes), device=dev)
+        outs, o = [], 0
+        for s in sizes:
+            outs.append(buf[o:o + s])
+            o += (s + 3) // 4 * 4
+        nb = lib.fs2_clf_head_wgrad_ws_bytes(n)
+        ws = K.ws(nb, dev)
+        lib.fs2_clf_head_wgrad(last, ldx, n, *w["head"], p, _p(seed) if p > 0 else None, self.site,
+                               K.ptr(demb), K.ptr(dlogit), *[_p(t) for t in outs], 0, _p(ws), nb,
+                               K.stream())
+        for i, lin in enumerate(self._head_layers()):
+            if i == 0 and detach:  # the classifier saw a detached embedding
+                continue
+            self._acc(lin.weight, outs[2 * i].view(lin.weight.shape))
+            self._acc(lin.bias, outs[2 * i + 1].view(lin.bias.shape))
+
+    def _lstm_wgrad(self, x, h, dgates, n_seq, steps):
+        dev, G = x.device, 4 * HIDDEN
+        dw_ih0 = torch.empty(G, NMELS, device=dev)
+        dw_ih_up = torch.empty(LAYERS - 1, G, HIDDEN, device=dev)
+        dw_hh = torch.empty(LAYERS, G, HIDDEN, device=dev)
+        db = torch.empty(LAYERS, G, device=dev)
+        K.lstm_stack_wgrad(x.view(n_seq * steps, NMELS), h, dgates, n_seq, steps, dw_ih0, dw_ih_up,
+                           dw_hh, db, beta=0)
+        for l in range(LAYERS):
+            P = lambda n: getattr(self.LSTM_stack, f"{n}_l{l}")
+            self._acc(P("weight_ih"), dw_ih0 if l == 0 else dw_ih_up[l - 1])
+            self._acc(P("weight_hh"), dw_hh[l])
+            self._acc(P("bias_ih"), db[l])  # b_ih and b_hh enter the gates as their sum
+            self._acc(P("bias_hh"), db[l])
 
 
 class _BCESumFn(torch.autograd.Function):
@@ -205,20 +289,41 @@ class _BCESumFn(torch.autograd.Function):
         return d, None
 
 
+class _GE2ESoftmaxFn(torch.autograd.Function):
+    """``get_similarity`` + ``get_softmax_loss`` (utils.py:77-90, 126-135) with ``w sim + b``
+    (speech_embedder_net.py:177), one kernel forward and one backward."""
+
+    @staticmethod
+    def forward(fctx, emb, w, b):
+        fctx.save_for_backward(emb, w, b)
+        return K.ge2e_softmax(emb, w.detach(), b.detach())
+
+    @staticmethod
+    def backward(fctx, g):
+        emb, w, b = fctx.saved_tensors
+        _, demb, dw, db = K.ge2e_softmax(emb, w.detach(), b.detach(), g=g.contiguous(),
+                                         grads=True)
+        return demb, dw, db
+
+
 class GE2ELoss(nn.Module):
     """``speech_embedder_net.py:165-186`` (softmax GE2E + BCE domain loss)."""
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", loss="softmax"):
         super().__init__()
         self.w = nn.Parameter(torch.tensor(10.0, device=device))
         self.b = nn.Parameter(torch.tensor(-5.0, device=device))
+        self.loss = loss  # hp.model.loss
 
     def forward(self, embeddings, lang_logits, langs, **kwargs):
         N, M, _ = embeddings.shape
+        if self.loss != "softmax":
+            raise NotImplementedError(f"hp.model.loss == {self.loss!r} is not built (the "
+                                      "reference's config uses 'softmax')")
         if M != 1:
-            raise NotImplementedError("GE2E similarity loss for M > 1 (speaker-encoder "
-                                      "pre-training) is outside the hot path")
-        loss = torch.full((), float("nan"), device=embeddings.device)  # utils.py:36, M - 1 = 0
+            loss = _GE2ESoftmaxFn.apply(embeddings.contiguous(), self.w, self.b)
+        else:  # utils.py:36, M - 1 = 0
+            loss = torch.full((), float("nan"), device=embeddings.device)
         da = _BCESumFn.apply(lang_logits.contiguous(), langs.contiguous().float()) \
             if lang_logits is not None else torch.zeros((), device=embeddings.device)
         return loss + da, loss, da

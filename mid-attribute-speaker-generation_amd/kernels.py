@@ -692,6 +692,54 @@ def adam_step(p, g, m, v, norm_coef, lr, beta1, beta2, eps, bc1, bc2_sqrt, hyper
                       ptr(hyper), stream())
 
 
+def adam_l2_step(p, g, m, v, norm_coef, lr, beta1, beta2, eps, weight_decay, step, hyper,
+                 gate=None):
+    """torch.optim.Adam with coupled L2 weight decay over flat buffers (fs2_adam_l2_step):
+    ``step`` device int64[1], ``hyper`` device float[3] scratch; a ``gate`` (device float) of 0
+    skips the call on the device, step count included."""
+    _dev(p, g, m, v, norm_coef, step, hyper, gate)
+    lib.fs2_adam_l2_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(norm_coef), float(lr),
+                         float(beta1), float(beta2), float(eps), float(weight_decay), ptr(step),
+                         ptr(hyper), ptr(gate), stream())
+
+
+def gate_lt(x, threshold):
+    """Device float 1.0 where x < threshold, else 0.0 (no host sync)."""
+    _dev(x)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    lib.fs2_gate_lt(ptr(x), float(threshold), ptr(out), stream())
+    return out
+
+
+def lstm_stack_wgrad(x, h, dgates, n_seq, steps, dw_ih0, dw_ih_up, dw_hh, db, beta=0):
+    """Weight gradients of the LSTM stack from x (rows, c_in), h (L, rows, H) and dgates
+    (L, rows, 4H), into the stack-layout outputs (fs2_lstm_stack_wgrad)."""
+    _dev(x, h, dgates, dw_ih0, dw_ih_up, dw_hh, db)
+    L, _, H = h.shape
+    c_in = x.shape[-1]
+    n = lib.fs2_lstm_stack_wgrad_ws_bytes(n_seq, steps, c_in, H, L)
+    w = ws(n, x.device)
+    lib.fs2_lstm_stack_wgrad(ptr(x), ptr(h), ptr(dgates), n_seq, steps, c_in, H, L, ptr(dw_ih0),
+                             ptr(dw_ih_up), ptr(dw_hh), ptr(db), int(beta), ptr(w), n, stream())
+
+
+def ge2e_softmax(emb, w, b, g=None, grads=False):
+    """GE2E softmax loss of emb (N, M, D); with ``grads`` also (demb, dw, db) scaled by the
+    device scalar ``g`` (fs2_ge2e_softmax)."""
+    _dev(emb, g)
+    N, M, D = emb.shape
+    dev = emb.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    demb = torch.empty_like(emb) if grads else None
+    dw = torch.empty((), dtype=torch.float32, device=dev) if grads else None
+    db = torch.empty((), dtype=torch.float32, device=dev) if grads else None
+    n = lib.fs2_ge2e_softmax_ws_bytes(N, M, D)
+    wk = ws(n, dev)
+    lib.fs2_ge2e_softmax(ptr(emb), N, M, D, ptr(w), ptr(b), ptr(g), ptr(loss), ptr(demb), ptr(dw),
+                         ptr(db), ptr(wk), n, stream())
+    return (loss, demb, dw, db) if grads else loss
+
+
 def sched_step(steps, hyper, init_lr, n_warmup, anneal_steps, anneal_rate, beta1, beta2,
                advance_lr=True):
     """Device-side LR schedule + Adam bias corrections for one step (fs2_sched_step)."""

@@ -43,6 +43,44 @@ def timeit(run, n=5):
     return s.elapsed_time(e) / n
 
 
+def wgrad_leg(n_seq, steps, L=3, c_in=80, n=10):
+    """--wgrad: the GE2E stack (80 -> 256 x 3) forward, backward and weight gradients alone at
+    n_seq x steps rows; FLOPs of the weight gradient = 2 rows 4H (c_in_l + H) summed over l."""
+    rows = n_seq * steps
+    xs = torch.randn(rows, c_in, device=dev)
+    wi0 = torch.randn(4 * H, c_in, device=dev) * 0.05
+    wiu = torch.randn(L - 1, 4 * H, H, device=dev) * 0.05
+    wh = torch.randn(L, 4 * H, H, device=dev) * 0.05
+    b = torch.randn(L, 4 * H, device=dev) * 0.05
+    wi0_t, wiu_t, wh_t = wi0.t().contiguous(), wiu.transpose(1, 2).contiguous(), wh.transpose(1, 2).contiguous()
+    g = torch.empty(rows, 4 * H, device=dev)
+    hs, cs = torch.empty(L, rows, H, device=dev), torch.empty(L, rows, H, device=dev)
+    a, dgs = torch.empty(L, rows, 4 * H, device=dev), torch.empty(L, rows, 4 * H, device=dev)
+    dcs, dxs = torch.empty(L * 2 * n_seq * H, device=dev), torch.empty(rows, c_in, device=dev)
+    dhs = torch.randn(rows, H, device=dev) * 0.01
+    outs = [torch.empty(4 * H, c_in, device=dev), torch.empty(L - 1, 4 * H, H, device=dev),
+            torch.empty(L, 4 * H, H, device=dev), torch.empty(L, 4 * H, device=dev)]
+    nb = lib.fs2_lstm_stack_wgrad_ws_bytes(n_seq, steps, c_in, H, L)
+    ws = torch.empty(nb // 4, device=dev)
+    f = lambda: lib.fs2_lstm_stack_fwd(P(xs), n_seq, steps, c_in, H, L, P(wi0), P(wiu), P(wh), P(b),
+                                       P(g), P(hs), P(cs), P(a), K.stream())
+    bw = lambda: lib.fs2_lstm_stack_bwd(P(dhs), n_seq, steps, c_in, H, L, P(wi0_t), P(wiu_t),
+                                        P(wh_t), P(a), P(cs), P(dgs), P(dcs), P(dxs), K.stream())
+    wg = lambda: lib.fs2_lstm_stack_wgrad(P(xs), P(hs), P(dgs), n_seq, steps, c_in, H, L,
+                                          *[P(t) for t in outs], 0, P(ws), nb, K.stream())
+    tf, tb, tw = timeit(f, n), timeit(bw, n), timeit(wg, n)
+    flop = 2.0 * rows * 4 * H * ((c_in + H) + (L - 1) * 2 * H)
+    print(f"stack {n_seq} x {steps}: fwd {tf:.3f} ms, bwd {tb:.3f} ms, wgrad {tw:.3f} ms "
+          f"({flop / 1e9:.1f} GF, {flop / tw / 1e9:.1f} TF/s, "
+          f"{100 * flop / tw / 1e9 / 155:.1f}% of the 155 TF f32-MFMA peak; "
+          f"workspace {nb / 2 ** 20:.1f} MiB)", flush=True)
+
+
+if "--wgrad" in sys.argv:
+    wgrad_leg(320, 150)  # N M = 32 x 10, the reference's training batch
+    wgrad_leg(192, 150)
+    sys.exit(0)
+
 if os.environ.get("LSTM_PROBE"):  # PMC probe: only the stacked kernels, a few launches
     L = 3
     w_ih_up = torch.randn(L - 1, 4 * H, H, device=dev) * 0.05
