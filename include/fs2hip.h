@@ -247,6 +247,43 @@ int64_t fs2_ge2e_softmax_ws_bytes(int64_t n_spk, int64_t m_utt, int64_t dim);
 int fs2_ge2e_softmax(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim, const float* w,
                      const float* b, const float* g, float* loss, float* demb, float* dw,
                      float* db, float* ws, int64_t ws_bytes, void* stream);
+/* Speaker-encoder batches cut on the device (data_load.py:107-110, 122-129):
+ *   out[r, t, c] = store[row_off[r] + c * row_stride[r] + row_start[r] + t],  t < len, c < n_mels.
+ * A row's source is one utterance stored (n_mels, frames) inside the flat corpus `store`:
+ * row_off its element offset (64-bit: a corpus may pass 2^31 elements), row_stride its frame
+ * count, row_start the crop start; the caller guarantees row_start + len <= row_stride.  The
+ * three descriptor arrays are device memory; out is (n_rows, len, n_mels).  1 <= len <= 256,
+ * 1 <= n_mels <= 128, n_rows >= 0 (0: nothing is launched).                               */
+int fs2_mel_crop_gather(const float* store, const int64_t* row_off, const int32_t* row_stride,
+                        const int32_t* row_start, int64_t n_rows, int64_t n_mels, int64_t len,
+                        float* out, void* stream);
+/* out[s] = m / ||m||, m the mean of rows seg_start[s] .. seg_start[s + 1] - 1 of x (rows, dim):
+ * the d-vector of generate_dvector (train_speech_embedder.py:75-78), one segment per
+ * utterance.  seg_start: device int64[n_seg + 1], non-decreasing; rows are added in row order
+ * (bitwise repeatable); an empty segment gives NaN, as torch's mean does.  dim <= 1024.    */
+int fs2_rows_mean_unit(const float* x, const int64_t* seg_start, int64_t n_seg, int64_t dim,
+                       float* out, void* stream);
+/* The scoring of test() (train_speech_embedder.py:425-450) for one batch, no host sync.
+ * enroll (n_spk, m_enr, dim), verify (n_spk, m_ver, dim), n_spk >= 2, m_ver >= 2, dim <= 256.
+ * sim (n_spk, m_ver, n_spk) = get_cossim(verify, get_centroids(enroll)) (utils.py:169-236):
+ * the cosine of verification utterance (j, i) with enrolment centroid k, but for k = j with the
+ * verification utterances' own exclude-self centroid; every entry + 1e-6.  table (50, 2) = FAR,
+ * FRR at thresholds float(0.01 i + 0.5), acceptance is sim > threshold:
+ *   FAR = (accepted - accepted same-speaker) / (n_spk - 1) / m_ver / n_spk,
+ *   FRR = (n_spk m_ver - accepted same-speaker) / m_ver / n_spk,
+ * from integer counts by fp32 divisions in that order.  result[4] = EER = (FAR + FRR) / 2,
+ * threshold, FAR, FRR at the first threshold with the strictly smallest |FAR - FRR| below 1;
+ * all zeros if none is.  ws: fs2_ge2e_eer_ws_bytes.                                       */
+int64_t fs2_ge2e_eer_ws_bytes(int64_t n_spk, int64_t dim);
+int fs2_ge2e_eer(const float* enroll, const float* verify, int64_t n_spk, int64_t m_enr,
+                 int64_t m_ver, int64_t dim, float* sim, float* table, float* result, float* ws,
+                 int64_t ws_bytes, void* stream);
+/* Epoch statistics kept on the device (train_speech_embedder.py:193-195, 278-279):
+ * totals (float[4]) += [loss[0], da_loss[0], 100 correct / n, 1] with correct =
+ * #{round(sigmoid(logit_i)) == y_i} (utils.py:238-247, round half to even).  loss, da_loss and
+ * logit are each nullable (their total then stays); correct (nullable) receives the count.   */
+int fs2_epoch_stats_add(float* totals, const float* loss, const float* da_loss, const float* logit,
+                        const float* y, int64_t n, float* correct, void* stream);
 /* BCEWithLogits per row (loss_rows, nullable) and dlogit = g[0] * scale * (sigmoid - y)
  * (g nullable = 1).                                                                      */
 int fs2_bce_logits(const float* logit, const float* y, int64_t n, float* loss_rows,

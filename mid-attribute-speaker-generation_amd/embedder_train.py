@@ -20,13 +20,22 @@ alone; the gate reproduces exactly that.
 line 181 (the model is named ``...woGE2E``), so only the domain loss trains the encoder and
 ``w``, ``b`` never move.  ``True`` is that line live.
 
-Not ported: the per-batch random shuffle / unshuffle of lines 160-172 -- the embedder treats
-the rows independently, so it only changes the order in which the gradient sums run; the
-dataset and mel extraction (librosa), the ``rescnn`` architecture, the EER ``test()``, the
-t-SNE plots, DDP of the embedder, and the joint ``train_ganlike.py`` loop.
+Around the step (``embedder_data.SpeakerBatcher`` supplies the batches, cut on the device):
+``train_epoch`` is the epoch loop of lines 146-216 with the loss, da_loss and da accuracy sums
+kept on the device and read once per epoch, ``da_subroutine`` lines 249-287 (one read per pass),
+``evaluate_eer`` the EER ``test()`` of 401-455 scored by ``fs2_ge2e_eer``, ``dvector`` the
+d-vector of 49-54 and 75-78 from a mel spectrogram, ``spkr2embedding`` lines 289-309.
+
+Not ported: the per-batch random shuffle / unshuffle of lines 160-172 is drawn by the batcher
+(to keep Python's generator in step with the reference) but not applied -- the embedder treats
+the rows independently, so it only changes the order in which the gradient sums run; the mel
+front end (librosa), the ``rescnn`` architecture, the ``contrast`` loss, the t-SNE plots, DDP of
+the embedder, and the joint ``train_ganlike.py`` loop.
 """
+import contextlib
 import math
 
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -99,6 +108,7 @@ class EmbedderTrainer:
         for o in opt.values():
             o.zero_grad()
         out = self.embedder(mels)
+        self.last_logits = out["da_lang_logits"].detach()  # for the epoch's accuracy
         emb = out["embeddings"].view(rows // n_utt, n_utt, -1)
         _, loss, da_loss = self.criterion(emb, out["da_lang_logits"], langs)
         gate = None  # None: da_pretrain, the domain loss always trains
@@ -124,12 +134,154 @@ class EmbedderTrainer:
         opt = self.optimizers["da"]
         opt.zero_grad()
         out = self.embedder(mels, detach=True)
+        self.last_logits = out["da_lang_logits"].detach()
         da_loss = _BCESumFn.apply(out["da_lang_logits"].contiguous(), langs.contiguous().float())
         da_loss.backward()
         n_da = opt.clip_grad_norm_(3.0)
         opt.step()
         self._weights_changed()
         return self._zero, da_loss.detach(), self._zero, self._zero, n_da
+
+    # -- epoch statistics: sums kept on the device, read once ---------------------------------
+    def _stats_new(self):
+        return K.zeros(4, self.device)
+
+    def _stats_add(self, totals, loss, da_loss, langs):
+        """totals += [loss, da_loss, accuracy (%) of the last step's logits, 1]."""
+        K.epoch_stats_add(totals, loss, da_loss, self.last_logits, langs.contiguous().float())
+
+    def _stats_read(self, totals):
+        return totals.tolist()  # the host read
+
+    def train_epoch(self, batcher, epoch, epochs, ge2e_backward=False):
+        """One epoch of train_speech_embedder.py:146-216 over ``batcher``
+        (``embedder_data.SpeakerBatcher``): a ``train_step`` per batch at ``progress = epoch /
+        epochs``, the sums of loss, da_loss and da accuracy kept on the device and read once
+        when the batches are queued, ``anneal(epoch)``, and past ``da_startpoint`` the
+        classifier subroutine (its pass averages are left in ``last_da_passes``).  Returns the
+        epoch's averages ``{"loss", "da_loss", "da_acc"}`` (accuracy in percent)."""
+        progress = float(epoch) / epochs
+        totals = self._stats_new()
+        for _ in range(batcher.batches_per_epoch):
+            mels, langs = batcher.next_batch()
+            loss, da_loss = self.train_step(mels, langs, progress, ge2e_backward)[:2]
+            self._stats_add(totals, loss, da_loss, langs)
+        self.anneal(epoch)
+        t = self._stats_read(totals)
+        stats = {"loss": t[0] / t[3], "da_loss": t[1] / t[3], "da_acc": t[2] / t[3]}
+        self.last_da_passes = None
+        if progress > self.da_startpoint:
+            self.last_da_passes = self.da_subroutine(batcher)
+        return stats
+
+    def da_subroutine(self, batcher, max_passes=10, floor=20.0):
+        """da_classifier_subroutine (249-287): passes of ``da_classifier_step`` over an epoch's
+        batches until a pass's average loss is below ``floor`` or above the previous pass's;
+        one host read per pass.  Returns the pass averages."""
+        prev, passes = float("inf"), []
+        for _ in range(max_passes):
+            totals = self._stats_new()
+            for _ in range(batcher.batches_per_epoch):
+                mels, langs = batcher.next_batch()
+                da_loss = self.da_classifier_step(mels, langs)[1]
+                self._stats_add(totals, None, da_loss, langs)
+            t = self._stats_read(totals)
+            avg = t[1] / t[3]
+            passes.append(avg)
+            if avg < floor or avg > prev:
+                break
+            prev = avg
+        return passes
+
+    @contextlib.contextmanager
+    def _eval(self):
+        """The embedder in eval mode without autograd; its mode is restored after."""
+        was = self.embedder.training
+        self.embedder.eval()
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            self.embedder.train(was)
+
+    def evaluate_eer(self, batches, epochs=1):
+        """test() (401-455): the average EER over ``epochs`` passes.  ``batches`` is a
+        ``SpeakerBatcher`` (an epoch of ``next_batch()`` per pass, M = its ``n_utt``) or a
+        sequence of ``(N, M, T, 80)`` device tensors.  Each batch's first M / 2 utterances per
+        speaker enrol, the rest verify (M even); both halves are embedded in eval mode and scored
+        by ``fs2_ge2e_eer``; the EERs are averaged on the device and read once at the end.  The
+        reference's permutation of the verification rows is undone before scoring and so leaves
+        the result alone; it is not drawn here."""
+        total = K.zeros(1, self.device)
+        with self._eval():
+            for _ in range(epochs):
+                if hasattr(batches, "next_batch"):
+                    it = (batches.next_batch()[0].view(batches.n_spk, batches.n_utt, -1,
+                                                       self.embedder.LSTM_stack.input_size)
+                          for _ in range(batches.batches_per_epoch))
+                else:
+                    it = iter(batches)
+                acc, n = K.zeros(1, self.device), 0
+                for mels in it:
+                    N, M, T, C = mels.shape
+                    if M % 2 or M < 4:
+                        raise ValueError(f"M = {M}: enrolment and verification halves need an "
+                                         "even M >= 4")
+                    emb = self.embedder.compute_embedding(mels.contiguous().view(N * M, T, C))
+                    emb = emb["embeddings"].view(N, M, -1)
+                    enroll, verify = emb[:, :M // 2].contiguous(), emb[:, M // 2:].contiguous()
+                    result = K.ge2e_eer(enroll, verify)[2]
+                    K.add(acc, result[0:1], out=acc)
+                    n += 1
+                if n == 0:
+                    raise ValueError("evaluate_eer: no batch")
+                K.scale_(acc, 1.0 / n)
+                K.add(total, acc, out=total)
+        return total.item() / epochs
+
+    def dvector(self, mel, seg=130):
+        """generate_dvector (49-54, 75-78) from a mel spectrogram: ``mel`` (80, F) on the device
+        gives the unit-length mean (64,) of the embeddings of its windows ``[s, s + seg)``,
+        ``s = 0, seg // 2, ...`` while ``s + seg <= F``; a list of mels gives (len, 64) from one
+        embedder call.  ``F < seg`` raises ``ValueError`` (the reference pads the waveform there,
+        which needs the mel front end this package does not have)."""
+        single = torch.is_tensor(mel)
+        mels = [mel] if single else list(mel)
+        off, stride, start, seg_start, base = [], [], [], [0], 0
+        for m in mels:
+            c, f = m.shape
+            if f < seg:
+                raise ValueError(f"{f} frames, fewer than one window of {seg}")
+            for s in range(0, f - seg + 1, seg // 2):
+                off.append(base)
+                stride.append(f)
+                start.append(s)
+            seg_start.append(len(off))
+            base += c * f
+        n_mels = mels[0].shape[0]
+        store = mels[0].contiguous().view(-1) if single else \
+            torch.cat([m.contiguous().view(-1) for m in mels])
+        dev = store.device
+
+        def up(a, dt):
+            return torch.from_numpy(np.asarray(a, dt)).pin_memory().to(dev, non_blocking=True)
+
+        windows = K.mel_crop_gather(store.float(), up(off, np.int64), up(stride, np.int32),
+                                    up(start, np.int32), n_mels, seg)
+        with self._eval():
+            emb = self.embedder.compute_embedding(windows)["embeddings"]
+            out = K.rows_mean_unit(emb.contiguous(), up(seg_start, np.int64))
+        return out[0] if single else out
+
+    def spkr2embedding(self, batcher, utter_num=400):
+        """get_spkr2embedding (289-309): ``{file name: (utter_num, 64) embeddings}`` of every
+        file of the batcher's store, in eval mode."""
+        out = {}
+        with self._eval():
+            for k, name in enumerate(batcher.store.files):
+                mels, _ = batcher.speaker_batch(k, utter_num)
+                out[name] = self.embedder.compute_embedding(mels)["embeddings"]
+        return out
 
     def anneal(self, epoch):
         """lr_schedule (83-95): halve the lr of ``main`` and ``ge2e`` at the anneal epochs."""

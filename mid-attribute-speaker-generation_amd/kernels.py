@@ -740,6 +740,67 @@ def ge2e_softmax(emb, w, b, g=None, grads=False):
     return (loss, demb, dw, db) if grads else loss
 
 
+def mel_crop_gather(store, row_off, row_stride, row_start, n_mels, length, out=None):
+    """out[r, t, c] = store[row_off[r] + c * row_stride[r] + row_start[r] + t]: crop, transpose
+    and stack utterances of a flat (n_mels, frames)-per-utterance corpus into (rows, length,
+    n_mels) (fs2_mel_crop_gather).  Descriptors: device int64 / int32 / int32, one per row."""
+    _dev(store, row_off, row_stride, row_start, out)
+    n = row_off.numel()
+    if (store.dtype, row_off.dtype, row_stride.dtype, row_start.dtype) != (
+            torch.float32, torch.int64, torch.int32, torch.int32):
+        raise RuntimeError("mel_crop_gather: store f32, row_off i64, row_stride / row_start i32")
+    if row_stride.numel() != n or row_start.numel() != n:
+        raise RuntimeError("mel_crop_gather: one descriptor of each kind per row")
+    if out is None:
+        out = torch.empty((n, int(length), int(n_mels)), dtype=torch.float32, device=store.device)
+    elif out.numel() != n * int(length) * int(n_mels) or out.dtype != torch.float32:
+        raise RuntimeError("mel_crop_gather: out is not f32 (rows, length, n_mels)")
+    lib.fs2_mel_crop_gather(ptr(store), ptr(row_off), ptr(row_stride), ptr(row_start), n,
+                            int(n_mels), int(length), ptr(out), stream())
+    return out
+
+
+def rows_mean_unit(x, seg_start):
+    """x (rows, dim), seg_start device int64 (n_seg + 1) -> (n_seg, dim): each segment's mean
+    row scaled to unit length (fs2_rows_mean_unit)."""
+    _dev(x, seg_start)
+    if x.dtype != torch.float32 or seg_start.dtype != torch.int64 or x.dim() != 2:
+        raise RuntimeError("rows_mean_unit: x f32 (rows, dim), seg_start i64")
+    n_seg = seg_start.numel() - 1
+    out = torch.empty((n_seg, x.shape[1]), dtype=torch.float32, device=x.device)
+    lib.fs2_rows_mean_unit(ptr(x), ptr(seg_start), n_seg, x.shape[1], ptr(out), stream())
+    return out
+
+
+def ge2e_eer(enroll, verify):
+    """test()'s scoring of one batch: enroll (N, M_e, D), verify (N, M_v, D) ->
+    sim (N, M_v, N), table (50, 2) = FAR, FRR per threshold, result (4) = EER, threshold, FAR,
+    FRR, all on the device (fs2_ge2e_eer)."""
+    _dev(enroll, verify)
+    N, Me, D = enroll.shape
+    Nv, Mv, Dv = verify.shape
+    if (Nv, Dv) != (N, D) or enroll.dtype != torch.float32 or verify.dtype != torch.float32:
+        raise RuntimeError("ge2e_eer: enroll (N, M_e, D) and verify (N, M_v, D), f32")
+    dev = enroll.device
+    sim = torch.empty((N, Mv, N), dtype=torch.float32, device=dev)
+    table = torch.empty((50, 2), dtype=torch.float32, device=dev)
+    result = torch.empty(4, dtype=torch.float32, device=dev)
+    n = lib.fs2_ge2e_eer_ws_bytes(N, D)
+    wk = ws(n, dev)
+    lib.fs2_ge2e_eer(ptr(enroll), ptr(verify), N, Me, Mv, D, ptr(sim), ptr(table), ptr(result),
+                     ptr(wk), n, stream())
+    return sim, table, result
+
+
+def epoch_stats_add(totals, loss=None, da_loss=None, logit=None, y=None, correct=None):
+    """totals (device float[4]) += [loss, da_loss, 100 * accuracy(logit, y), 1] without a host
+    read; ``correct`` (device float) receives the count of right labels (fs2_epoch_stats_add)."""
+    _dev(totals, loss, da_loss, logit, y, correct)
+    n = logit.numel() if logit is not None else 0
+    lib.fs2_epoch_stats_add(ptr(totals), ptr(loss), ptr(da_loss), ptr(logit), ptr(y), n,
+                            ptr(correct), stream())
+
+
 def sched_step(steps, hyper, init_lr, n_warmup, anneal_steps, anneal_rate, beta1, beta2,
                advance_lr=True):
     """Device-side LR schedule + Adam bias corrections for one step (fs2_sched_step)."""
