@@ -284,6 +284,27 @@ int fs2_ge2e_eer(const float* enroll, const float* verify, int64_t n_spk, int64_
  * logit are each nullable (their total then stays); correct (nullable) receives the count.   */
 int fs2_epoch_stats_add(float* totals, const float* loss, const float* da_loss, const float* logit,
                         const float* y, int64_t n, float* correct, void* stream);
+/* The mel front end (preprocessor/preprocessor.py:330-336; common/layers.py:101-123 over
+ * common/stft.py) of a ragged batch in one launch: wav (batch, samples) fp32, lens (device
+ * int64, nullable = samples for every row; read clamped into [1, samples]).  Per row, frames
+ * f < n_frames = 1 + len / hop of the centred STFT (n_fft = win_length = 1024, reflect padding
+ * of 512 resolved against the row's own len: index -k is k, len - 1 + k is len - 1 - k, every
+ * index clamped into [0, len - 1]); F_max = 1 + samples / hop:
+ *   mag    (batch, 513, F_max)  |STFT| (nullable)
+ *   energy (batch, F_max)       ||mag[:, f]||_2 (nullable)
+ *   mel    (batch, n_mels, F_max)  log(max(filterbank . mag, 1e-5))
+ * and zeros at f >= n_frames.  window (1024) fp32; twiddle (1024, 2) fp32 = cos, -sin of
+ * 2 pi k / 1024 rounded from fp64; the filterbank in compressed form: filter c weighs bins
+ * fb_first[c] .. fb_first[c] + fb_count[c] - 1 with fb_w[fb_off[c] ..] (device int32 x 3,
+ * n_weights floats; ranges are clamped to the 513 bins and the n_weights floats).  clip != 0
+ * clamps the samples to [-1, 1] on load; log_mag != 0 stores log(max(mag, 1e-5)) in mag
+ * (linear_spectrogram, layers.py:120-123).  1 <= hop <= 1024, n_mels <= 128; any other n_fft is
+ * an argument error.  A frame's result does not depend on its place in the batch.         */
+int fs2_melspec(const float* wav, const int64_t* lens, int64_t batch, int64_t samples,
+                int64_t n_fft, int64_t hop, const float* window, const float* twiddle,
+                const int32_t* fb_first, const int32_t* fb_count, const int32_t* fb_off,
+                const float* fb_w, int64_t n_weights, int64_t n_mels, int clip, int log_mag,
+                float* mel, float* energy, float* mag, int64_t* n_frames, void* stream);
 /* BCEWithLogits per row (loss_rows, nullable) and dlogit = g[0] * scale * (sigmoid - y)
  * (g nullable = 1).                                                                      */
 int fs2_bce_logits(const float* logit, const float* y, int64_t n, float* loss_rows,

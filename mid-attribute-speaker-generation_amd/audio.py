@@ -1,0 +1,177 @@
+"""The mel front end: waveform -> log-mel spectrogram, frame energy, linear spectrogram.
+
+One kernel (``fs2_melspec``) serves the three places the reference computes them:
+
+  preprocessor/preprocessor.py:330-336   ``calc_spectrogram`` (torchaudio Spectrogram + MelScale;
+                                         clip to [-1, 1], log-mel and the L2 frame energy)
+  common/layers.py:101-123               ``TacotronSTFT.mel_spectrogram`` / ``linear_spectrogram``
+                                         of the speaker encoder (librosa filterbank, conv STFT)
+  train_speech_embedder.py:27-81         ``generate_dvector``'s mel of a wav
+                                         (``EmbedderTrainer.dvector_from_wav``)
+
+They are the same arithmetic: periodic Hann window of 1024, hop 256, centred frames with reflect
+padding of 512, the magnitude of the 513 bins, the Slaney mel filterbank (80 filters, 0-8000 Hz at
+22 050 Hz, area normalised) and ``log(clamp(., 1e-5))``.  Everything on the host here is table
+construction (fp64, rounded to fp32); the arithmetic on samples runs in the kernel.
+"""
+import numpy as np
+import torch
+
+from . import kernels as K
+from .config import load_configs
+
+N_FFT = 1024  # compiled into the kernel (n_fft = win_length)
+N_BINS = N_FFT // 2 + 1
+
+
+def _hz_to_mel(f):
+    """Slaney's scale: 200/3 Hz per mel below 1 kHz, ln(6.4)/27 per mel above."""
+    f = np.asarray(f, np.float64)
+    lin = f / (200.0 / 3.0)
+    log = 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0)
+    return np.where(f >= 1000.0, log, lin)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), m * (200.0 / 3.0))
+
+
+def mel_filterbank(sr, n_fft, n_mels, fmin, fmax):
+    """The Slaney filterbank (n_mels, n_fft // 2 + 1) that ``librosa.filters.mel`` (defaults:
+    ``htk=False``, area norm) and ``torchaudio.transforms.MelScale(norm="slaney",
+    mel_scale="slaney")`` both build: triangles between consecutive mel points over
+    ``linspace(0, sr / 2, n_fft // 2 + 1)``, each scaled by ``2 / (f[m + 2] - f[m])``; fp64,
+    rounded to fp32."""
+    freqs = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
+    pts = _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), n_mels + 2))
+    diff = np.diff(pts)
+    ramps = pts[:, None] - freqs[None, :]
+    lower = -ramps[:-2] / diff[:-1, None]
+    upper = ramps[2:] / diff[1:, None]
+    fb = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (pts[2:] - pts[:-2]))[:, None]
+    return fb.astype(np.float32)
+
+
+def compress_filterbank(dense):
+    """A dense (n_mels, bins) matrix as ``(first, count, offset, weights)``: filter ``c`` weighs
+    bins ``first[c] .. first[c] + count[c] - 1`` (its first to its last non-zero column) with
+    ``weights[offset[c]:offset[c] + count[c]]``.  int32 x 3 and float32; an all-zero row has
+    count 0."""
+    dense = np.asarray(dense, np.float32)
+    first, count, off, w = [], [], [], []
+    for row in dense:
+        nz = np.flatnonzero(row)
+        lo, n = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
+        first.append(lo)
+        count.append(n)
+        off.append(sum(count[:-1]))
+        w.append(row[lo:lo + n])
+    weights = np.concatenate(w) if w else np.zeros(0, np.float32)
+    return (np.asarray(first, np.int32), np.asarray(count, np.int32), np.asarray(off, np.int32),
+            weights.astype(np.float32))
+
+
+def expand_filterbank(first, count, off, weights, bins=N_BINS):
+    """The dense matrix of a compressed filterbank (the inverse of ``compress_filterbank``)."""
+    dense = np.zeros((len(first), bins), np.float32)
+    for c, (lo, n, o) in enumerate(zip(first, count, off)):
+        dense[c, lo:lo + n] = weights[o:o + n]
+    return dense
+
+
+def twiddle_table():
+    """(1024, 2) float32: cos and -sin of 2 pi k / 1024, computed in fp64."""
+    ang = 2.0 * np.pi * np.arange(N_FFT, dtype=np.float64) / N_FFT
+    return np.stack([np.cos(ang), -np.sin(ang)], axis=1).astype(np.float32)
+
+
+def frame_count(length, hop):
+    """Frames of a centred STFT over ``length`` samples: ``1 + length // hop``."""
+    return 1 + int(length) // int(hop)
+
+
+class MelFrontEnd:
+    """The front end with the parameters of ``preprocess.yaml`` (the speaker encoder's
+    ``config.yaml`` has the same values).  Tables are built on the host at construction and go to
+    ``device`` at the first call."""
+
+    def __init__(self, preprocess_config=None, device="cuda"):
+        from scipy.signal import get_window
+        pp = preprocess_config if preprocess_config is not None else load_configs()[0]
+        stft, mel = pp["stft"], pp.get("mel", {})
+        n_fft, win = int(stft["filter_length"]), int(stft.get("win_length", stft["filter_length"]))
+        if n_fft != N_FFT or win != N_FFT:
+            raise ValueError(f"filter_length {n_fft}, win_length {win}: the kernel is built for "
+                             f"n_fft = win_length = {N_FFT}")
+        self.hop = int(stft["hop_length"])
+        if not 1 <= self.hop <= N_FFT:
+            raise ValueError(f"hop_length {self.hop} (1..{N_FFT})")
+        self.sr = int(pp["audio"]["sampling_rate"])
+        self.n_mels = int(mel.get("n_mel_channels", 80))
+        self.fmin, self.fmax = float(mel.get("mel_fmin", 0.0)), float(mel.get("mel_fmax", 8000.0))
+        self.device = torch.device(device)
+        self.window = get_window("hann", N_FFT, fftbins=True).astype(np.float32)
+        self.mel_basis = mel_filterbank(self.sr, N_FFT, self.n_mels, self.fmin, self.fmax)
+        self._tables = None
+
+    def _dev_tables(self):
+        if self._tables is None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+            self._tables = (up(self.window), up(twiddle_table()),
+                            tuple(up(a) for a in compress_filterbank(self.mel_basis)))
+        return self._tables
+
+    def check_lens(self, lens, samples):
+        """The reflect-pad condition torch enforces, for host lengths: ``512 < len <= S``."""
+        for n in lens:
+            if not N_FFT // 2 < int(n) <= int(samples):
+                raise ValueError(f"length {int(n)}: reflect padding of {N_FFT // 2} needs "
+                                 f"{N_FFT // 2} < len <= {int(samples)} samples")
+
+    def n_frames(self, length):
+        return frame_count(length, self.hop)
+
+    def __call__(self, wav, lens=None, clip=False, mag=False, log_mag=False):
+        """wav (B, S) or (S,) on the device -> ``(logmel (B, n_mels, F), energy (B, F),
+        n_frames (B) int64[, mag (B, 513, F)])``, F = 1 + S // hop, zeros past ``n_frames``
+        (without the batch axis for a 1-D wav).  ``lens``: None (S for every row), a list
+        (checked on the host) or a device int64 tensor (not read back)."""
+        single = wav.dim() == 1
+        w = (wav[None] if single else wav).contiguous()
+        if w.dtype != torch.float32:
+            w = w.float()
+        B, S = w.shape
+        if lens is None:
+            self.check_lens([S], S)
+        elif not torch.is_tensor(lens):
+            lens = [int(n) for n in lens]
+            if len(lens) != B:
+                raise ValueError(f"{len(lens)} lengths for {B} rows")
+            self.check_lens(lens, S)
+            lens = torch.from_numpy(np.asarray(lens, np.int64)).pin_memory().to(w.device,
+                                                                                 non_blocking=True)
+        window, twiddle, fb = self._dev_tables()
+        mel_o, en_o, mag_o, nf = K.melspec(w, lens, self.hop, window, twiddle, fb, self.n_mels,
+                                           clip=clip, energy=True, mag=mag or log_mag,
+                                           log_mag=log_mag)
+        out = (mel_o, en_o, nf) + ((mag_o,) if mag or log_mag else ())
+        return tuple(o[0] for o in out) if single else out
+
+    def calc_spectrogram(self, audio):
+        """``Preprocessor.calc_spectrogram`` (preprocessor.py:330-336): a numpy waveform ->
+        numpy ``(n_mels, F)`` float32 log-mel and ``(F,)`` float32 energy, samples clipped to
+        [-1, 1]."""
+        wav = torch.from_numpy(np.ascontiguousarray(audio, np.float32)).to(self.device)
+        mel, energy, _ = self(wav, clip=True)
+        return mel.cpu().numpy(), energy.cpu().numpy()
+
+    def mel_spectrogram(self, y):
+        """``TacotronSTFT.mel_spectrogram`` (layers.py:101-118): y (B, T) in [-1, 1] ->
+        (B, n_mels, F).  The reference's range asserts (two host reads) are not made."""
+        return self(y)[0]
+
+    def linear_spectrogram(self, y):
+        """``TacotronSTFT.linear_spectrogram`` (layers.py:120-123): (B, T) -> (B, 513, F),
+        ``log(clamp(|STFT|, 1e-5))``."""
+        return self(y, log_mag=True)[3]

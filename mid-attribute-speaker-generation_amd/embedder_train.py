@@ -24,13 +24,15 @@ Around the step (``embedder_data.SpeakerBatcher`` supplies the batches, cut on t
 ``train_epoch`` is the epoch loop of lines 146-216 with the loss, da_loss and da accuracy sums
 kept on the device and read once per epoch, ``da_subroutine`` lines 249-287 (one read per pass),
 ``evaluate_eer`` the EER ``test()`` of 401-455 scored by ``fs2_ge2e_eer``, ``dvector`` the
-d-vector of 49-54 and 75-78 from a mel spectrogram, ``spkr2embedding`` lines 289-309.
+d-vector of 49-54 and 75-78 from a mel spectrogram, ``dvector_from_wav`` the same from a
+waveform through the mel front end (``audio.py``), ``spkr2embedding`` lines 289-309.
 
 Not ported: the per-batch random shuffle / unshuffle of lines 160-172 is drawn by the batcher
 (to keep Python's generator in step with the reference) but not applied -- the embedder treats
-the rows independently, so it only changes the order in which the gradient sums run; the mel
-front end (librosa), the ``rescnn`` architecture, the ``contrast`` loss, the t-SNE plots, DDP of
-the embedder, and the joint ``train_ganlike.py`` loop.
+the rows independently, so it only changes the order in which the gradient sums run; the
+silence split of ``process_dvector_wav`` (``librosa.effects.split``), the ``rescnn``
+architecture, the ``contrast`` loss, the t-SNE plots, DDP of the embedder, and the joint
+``train_ganlike.py`` loop.
 """
 import contextlib
 import math
@@ -243,8 +245,8 @@ class EmbedderTrainer:
         """generate_dvector (49-54, 75-78) from a mel spectrogram: ``mel`` (80, F) on the device
         gives the unit-length mean (64,) of the embeddings of its windows ``[s, s + seg)``,
         ``s = 0, seg // 2, ...`` while ``s + seg <= F``; a list of mels gives (len, 64) from one
-        embedder call.  ``F < seg`` raises ``ValueError`` (the reference pads the waveform there,
-        which needs the mel front end this package does not have)."""
+        embedder call.  ``F < seg`` raises ``ValueError`` (the reference pads the waveform there:
+        ``dvector_from_wav``)."""
         single = torch.is_tensor(mel)
         mels = [mel] if single else list(mel)
         off, stride, start, seg_start, base = [], [], [], [0], 0
@@ -267,6 +269,78 @@ class EmbedderTrainer:
             return torch.from_numpy(np.asarray(a, dt)).pin_memory().to(dev, non_blocking=True)
 
         windows = K.mel_crop_gather(store.float(), up(off, np.int64), up(stride, np.int32),
+                                    up(start, np.int32), n_mels, seg)
+        with self._eval():
+            emb = self.embedder.compute_embedding(windows)["embeddings"]
+            out = K.rows_mean_unit(emb.contiguous(), up(seg_start, np.int64))
+        return out[0] if single else out
+
+    @staticmethod
+    def _check_wav_lens(lens, rows, samples):
+        if len(lens) != rows or any(not 1 <= n <= samples for n in lens):
+            raise ValueError(f"lengths {lens} for {rows} waveforms of {samples} samples")
+
+    def dvector_from_wav(self, wav, lens=None, seg=130):
+        """generate_dvector (27-81) from a waveform on the device: the mel front end
+        (``audio.MelFrontEnd``), then the window cut, embedder and unit-length mean of
+        ``dvector``.  ``wav`` is (S,) -> (64,), (B, S) with ``lens`` -> (B, 64), or a list of 1-D
+        waveforms -> (len, 64).  ``lens`` as a list costs no synchronisation; as a device tensor
+        it is read once (the window descriptors are built on the host).
+
+        A waveform shorter than ``seg * hop + 1024`` samples is zero-extended to that length
+        first, which is what ``process_dvector_wav`` lines 29-47 intend.  As shipped, that
+        function multiplies a hop that is already in samples by the sample rate, so its bound is
+        7.6e8 samples and it zero-pads every input to that length.  ``librosa.effects.split(
+        top_db=100)`` is not built: the whole utterance is one interval, which is what that call
+        returns for any signal with no stretch 100 dB below its peak."""
+        from .audio import MelFrontEnd, N_FFT
+        if getattr(self, "_front_end", None) is None:
+            self._front_end = MelFrontEnd(device=self.device)
+        front_end = self._front_end
+        hop, need = front_end.hop, seg * front_end.hop + N_FFT
+        single = torch.is_tensor(wav) and wav.dim() == 1
+        if torch.is_tensor(wav):
+            w = wav[None] if single else wav
+            if lens is None:
+                lens = [w.shape[1]] * w.shape[0]
+            elif torch.is_tensor(lens):
+                lens = lens.tolist()
+            lens = [int(n) for n in lens]
+            self._check_wav_lens(lens, w.shape[0], w.shape[1])
+            short = any(n < need for n in lens)
+            if w.shape[1] < need:
+                w = torch.nn.functional.pad(w.float(), (0, need - w.shape[1]))
+            elif short:
+                w = w.float().clone()
+        else:
+            rows = list(wav)
+            lens = [int(r.numel()) for r in rows]
+            self._check_wav_lens(lens, len(rows), max(lens))
+            w = torch.zeros((len(rows), max(max(lens), need)), dtype=torch.float32,
+                            device=rows[0].device)
+            for b, r in enumerate(rows):
+                w[b, :lens[b]] = r
+            short = False  # the rows are zero past their lengths already
+        if short:
+            for b, n in enumerate(lens):
+                if n < need:
+                    w[b, n:need] = 0.0
+        lens = [max(n, need) for n in lens]
+        mel, _, _ = front_end(w, lens=lens)
+        B, n_mels, f_max = mel.shape
+        off, stride, start, seg_start = [], [], [], [0]
+        for b, n in enumerate(lens):
+            for s in range(0, 1 + n // hop - seg + 1, seg // 2):
+                off.append(b * n_mels * f_max)
+                stride.append(f_max)
+                start.append(s)
+            seg_start.append(len(off))
+        dev = mel.device
+
+        def up(a, dt):
+            return torch.from_numpy(np.asarray(a, dt)).pin_memory().to(dev, non_blocking=True)
+
+        windows = K.mel_crop_gather(mel.view(-1), up(off, np.int64), up(stride, np.int32),
                                     up(start, np.int32), n_mels, seg)
         with self._eval():
             emb = self.embedder.compute_embedding(windows)["embeddings"]

@@ -772,6 +772,50 @@ def rows_mean_unit(x, seg_start):
     return out
 
 
+def melspec(wav, lens, hop, window, twiddle, fb, n_mels, clip=False, energy=True, mag=False,
+            log_mag=False, n_fft=1024, out=None):
+    """The mel front end of a ragged batch (fs2_melspec): wav (B, S) f32, lens device int64 (B)
+    or None -> ``(mel (B, n_mels, F), energy (B, F) or None, mag (B, 513, F) or None,
+    n_frames (B) int64)``, F = 1 + S // hop, zeros at frames past ``n_frames``.  ``fb`` is the
+    compressed filterbank ``(first, count, offset, weights)`` on the device (int32 x 3, f32);
+    ``window`` (1024) and ``twiddle`` (1024, 2) f32.  ``out`` = preallocated
+    ``(mel, energy, mag, n_frames)`` (energy / mag may be None there)."""
+    first, count, off, w = fb
+    _dev(wav, lens, window, twiddle, first, count, off, w)
+    if wav.dim() != 2 or wav.dtype != torch.float32:
+        raise RuntimeError("melspec: wav is f32 (B, S)")
+    if lens is not None and (lens.dtype != torch.int64 or lens.numel() != wav.shape[0]):
+        raise RuntimeError("melspec: lens is int64 (B)")
+    if window.dtype != torch.float32 or window.numel() != 1024 or \
+            twiddle.dtype != torch.float32 or twiddle.numel() != 2048:
+        raise RuntimeError("melspec: window f32 (1024), twiddle f32 (1024, 2)")
+    if (first.dtype, count.dtype, off.dtype, w.dtype) != (torch.int32,) * 3 + (torch.float32,) or \
+            not first.numel() == count.numel() == off.numel() == int(n_mels):
+        raise RuntimeError("melspec: filterbank is (first, count, offset) int32 (n_mels) + f32 weights")
+    B, S = wav.shape
+    hop = int(hop)
+    if not 1 <= hop <= 1024:
+        raise RuntimeError(f"melspec: hop {hop} (1..1024)")
+    F, dev = 1 + S // hop, wav.device
+    if out is None:
+        out = (torch.empty((B, int(n_mels), F), dtype=torch.float32, device=dev),
+               torch.empty((B, F), dtype=torch.float32, device=dev) if energy else None,
+               torch.empty((B, 513, F), dtype=torch.float32, device=dev) if mag else None,
+               torch.empty(B, dtype=torch.int64, device=dev))
+    mel_o, en_o, mag_o, nf_o = out
+    _dev(mel_o, en_o, mag_o, nf_o)
+    if mel_o.dtype != torch.float32 or mel_o.numel() != B * int(n_mels) * F or \
+            (en_o is not None and (en_o.dtype != torch.float32 or en_o.numel() != B * F)) or \
+            (mag_o is not None and (mag_o.dtype != torch.float32 or mag_o.numel() != B * 513 * F)) or \
+            nf_o.dtype != torch.int64 or nf_o.numel() != B:
+        raise RuntimeError("melspec: out is (mel (B, n_mels, F), energy (B, F), mag (B, 513, F)) "
+                           "f32 and n_frames (B) int64")
+    lib.fs2_melspec(ptr(wav), ptr(lens), B, S, int(n_fft), hop, ptr(window), ptr(twiddle),
+                    ptr(first), ptr(count), ptr(off), ptr(w), w.numel(), int(n_mels), int(bool(clip)),
+                    int(bool(log_mag)), ptr(mel_o), ptr(en_o), ptr(mag_o), ptr(nf_o), stream())
+    return mel_o, en_o, mag_o, nf_o
+
+
 def ge2e_eer(enroll, verify):
     """test()'s scoring of one batch: enroll (N, M_e, D), verify (N, M_v, D) ->
     sim (N, M_v, N), table (50, 2) = FAR, FRR per threshold, result (4) = EER, threshold, FAR,

@@ -8,7 +8,8 @@ runs in eval mode with the p/e/d controls, the PostNet mel ``(B, T, 80)`` goes t
 in its row layout (the reference transposes it to ``(B, 80, T)`` first), and each waveform is
 cropped to ``mel_len * hop_length`` samples as int16 PCM.  Figures and .wav files
 (``synth_samples``' plotting / ``wavfile.write``) are outside the hot path; the arrays are
-returned instead.
+returned instead.  ``synth_dvectors`` goes on from the vocoder's fp32 waveform through the mel
+front end and the speaker encoder to the d-vector of each synthesised utterance, on the device.
 """
 import torch
 
@@ -36,6 +37,30 @@ def synth_batch(model, vocoder, batch, control_values=(1.0, 1.0, 1.0), hop_lengt
     pcm = pcm.view(B, -1)
     wavs = [pcm[i, : lengths[i]].cpu().numpy() for i in range(B)]
     return out, wavs
+
+
+@torch.no_grad()
+def synth_dvectors(model, vocoder, trainer, batch, control_values=(1.0, 1.0, 1.0), hop_length=256):
+    """Who does the synthesised voice sound like: one device batch (as ``synth_batch`` takes) ->
+    (model output tuple, d-vectors (B, 64) on the device).  The model runs in eval mode, the
+    vocoder keeps its fp32 waveform on the device (``pcm=False``), the mel front end reads it as
+    (B, T * hop_length) with ``lens = mel_len * hop_length``, and
+    ``EmbedderTrainer.dvector_from_wav`` cuts the windows and embeds them.  Nothing goes to the
+    host in between but the one read of ``mel_len`` that ``synth_batch`` makes too."""
+    p_c, e_c, d_c = control_values
+    speaker_meta = batch[-2].view(batch[-2].shape[0] if batch[-2].dim() > 1 else 1, -1)
+    was = model.training
+    model.eval()
+    try:
+        out = model(*batch[:-2][2:], p_control=p_c, e_control=e_c, d_control=d_c, accents=batch[-1],
+                    speaker_meta=speaker_meta)
+    finally:
+        model.train(was)
+    post, mel_len = out[1], out[9]
+    B, T, C = post.shape
+    wav, _ = vocoder.forward_rows(post.reshape(B * T, C), B, T, pcm=False, lengths=mel_len)
+    lens = (mel_len * hop_length).tolist()
+    return out, trainer.dvector_from_wav(wav.view(B, -1), lens=lens)
 
 
 def synthesize(model, configs, vocoder, batchs, control_values):
