@@ -305,6 +305,51 @@ int fs2_melspec(const float* wav, const int64_t* lens, int64_t batch, int64_t sa
                 const int32_t* fb_first, const int32_t* fb_count, const int32_t* fb_off,
                 const float* fb_w, int64_t n_weights, int64_t n_mels, int clip, int log_mag,
                 float* mel, float* energy, float* mag, int64_t* n_frames, void* stream);
+/* The F0 contour of a ragged batch by YIN (de Cheveigne & Kawahara 2002), the estimator that
+ * stands where preprocessor/preprocessor.py:196-201 calls pyworld (no parity with DIO is
+ * claimed).  wav (batch, samples) fp32, lens (device int64, nullable = samples; read clamped
+ * into [0, samples]).  Per row, frames k < n_frames = 1 + len / hop centred at k hop (the
+ * frames of fs2_melspec); F_max = 1 + samples / hop; W = 512 (compiled in),
+ * tau_max = floor(sr / f0_floor) <= 512, tau_min = ceil(sr / f0_ceil) >= 1, L = W + tau_max:
+ *   s[j]     = wav[k hop - L / 2 + j], 0 <= j < L, zero outside [0, len)
+ *   d(tau)   = sum_{j < W} (s[j] - s[j + tau])^2, fp32, j ascending, no fused multiply-add
+ *   d'(0)    = 1, d'(tau) = d(tau) tau / sum_{1 <= j <= tau} d(j) (1 where that sum is 0)
+ *   tau      = the first in [tau_min, tau_max] with d'(tau) < threshold, advanced while
+ *              d'(tau + 1) < d'(tau); none: f0 = 0, dip = min d' over the range
+ *   dip      = d'(tau); for 1 <= tau < tau_max a parabola through d'(tau - 1 .. tau + 1) moves
+ *              tau by 0.5 (a - c) / (a - 2 b + c), clamped to +-1, 0 unless the curvature is
+ *              positive; f0 = sr / (tau + offset), 0 when outside [f0_floor, f0_ceil]
+ * f0, dip (batch, F_max) fp32, zeros at k >= n_frames; n_frames (batch) int64.  A frame's
+ * result depends on its samples only, never on its place in the batch.                     */
+int fs2_f0_yin(const float* wav, const int64_t* lens, int64_t batch, int64_t samples, int64_t hop,
+               double sr, double f0_floor, double f0_ceil, double threshold, float* f0, float* dip,
+               int64_t* n_frames, void* stream);
+/* preprocessor.py:213-221 in place: per row of x (batch, frames) fp32 with n[b] live frames
+ * (device int64, nullable = frames; clamped into [0, frames]), every zero frame becomes the
+ * line between its non-zero neighbours (fp64, rounded once), the first non-zero value before
+ * it and the last after it; ok[b] (int32) = count_nonzero > 1, and a row with ok = 0 is left
+ * as it was (the reference returns None there, line 204).  frames <= 15360.                */
+int fs2_pitch_fill(float* x, const int64_t* n, int64_t batch, int64_t frames, int32_t* ok,
+                   void* stream);
+/* preprocessor.py:223-242: out[b, i] = mean(x[b, pos : pos + d[b, i]]) (fp64 sum, rounded once)
+ * or 0 where d = 0, pos the running sum of d; durations (batch, phones) int64, n as above.
+ * The reference's in-place order is kept: x[b, i] is overwritten with the mean as it goes (for
+ * i < frames), so a phoneme whose pos fell behind i after zero durations averages values already
+ * written.  The slice is cut at n[b] as numpy cuts it; an empty slice of a non-zero duration
+ * gives NaN as np.mean does.  frames <= 15360.                                             */
+int fs2_segment_mean(float* x, const int64_t* n, const int64_t* durations, int64_t batch,
+                     int64_t frames, int64_t phones, float* out, void* stream);
+/* remove_outlier (preprocessor.py:307-315) then StandardScaler.partial_fit (94-97) per row, rows
+ * in order: sorted (batch, cols) fp32 ascending with n[b] live values first; the 25th and 75th
+ * percentiles by numpy's linear rule in fp64, survivors lower < v < upper, their count, mean and
+ * M2 in fp64, merged into state (device double[3] = n, mean, M2) by Chan's formula.  A row with
+ * no survivor contributes nothing.                                                        */
+int fs2_outlier_moments(const float* sorted, const int64_t* n, int64_t batch, int64_t cols,
+                        double* state, void* stream);
+/* normalize (preprocessor.py:317-328): x[b, i] = (x[b, i] - mean) / std (fp64, rounded once) over
+ * i < n[b], and minmax (device double[2]) = min, max of itself and the stored values.      */
+int fs2_normalize_minmax(float* x, const int64_t* n, int64_t batch, int64_t cols, double mean,
+                         double std, double* minmax, void* stream);
 /* BCEWithLogits per row (loss_rows, nullable) and dlogit = g[0] * scale * (sigmoid - y)
  * (g nullable = 1).                                                                      */
 int fs2_bce_logits(const float* logit, const float* y, int64_t n, float* loss_rows,

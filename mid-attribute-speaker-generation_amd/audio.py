@@ -175,3 +175,52 @@ class MelFrontEnd:
         """``TacotronSTFT.linear_spectrogram`` (layers.py:120-123): (B, T) -> (B, 513, F),
         ``log(clamp(|STFT|, 1e-5))``."""
         return self(y, log_mag=True)[3]
+
+
+class PitchExtractor:
+    """The F0 contour on the frames of ``MelFrontEnd`` (centres ``k * hop``, ``1 + len // hop`` of
+    them: the count ``pw.dio`` returns for ``frame_period = hop / sr``), by YIN
+    (``fs2_f0_yin``).  The reference (preprocessor.py:196-201) calls pyworld's DIO + StoneMask;
+    this is another estimator and its values are not DIO's.  ``dip`` is the normalised
+    difference function at the chosen lag (its minimum over the lag range for an unvoiced
+    frame): small means strongly periodic."""
+
+    def __init__(self, preprocess_config=None, device="cuda", f0_floor=71.0, f0_ceil=800.0,
+                 threshold=0.15):
+        pp = preprocess_config if preprocess_config is not None else load_configs()[0]
+        self.hop = int(pp["stft"]["hop_length"])
+        self.sr = int(pp["audio"]["sampling_rate"])
+        self.f0_floor, self.f0_ceil, self.threshold = float(f0_floor), float(f0_ceil), float(threshold)
+        if not 1 <= self.hop <= N_FFT:
+            raise ValueError(f"hop_length {self.hop} (1..{N_FFT})")
+        if not 0.0 < self.f0_floor <= self.f0_ceil <= self.sr or not self.threshold > 0.0:
+            raise ValueError(f"f0 range {f0_floor}..{f0_ceil} at {self.sr} Hz, threshold {threshold}")
+        if self.sr // self.f0_floor > 512:
+            raise ValueError(f"f0_floor {f0_floor} at {self.sr} Hz needs {int(self.sr // self.f0_floor)} "
+                             "lags: the kernel is built for at most 512")
+        self.device = torch.device(device)
+
+    def n_frames(self, length):
+        return frame_count(length, self.hop)
+
+    def __call__(self, wav, lens=None):
+        """wav (B, S) or (S,) on the device -> ``(f0 (B, F), dip (B, F), n_frames (B) int64)``,
+        F = 1 + S // hop, zeros past ``n_frames`` (without the batch axis for a 1-D wav).
+        ``lens`` as in ``MelFrontEnd.__call__``: None, a host list (checked) or a device int64
+        tensor (not read back)."""
+        single = wav.dim() == 1
+        w = (wav[None] if single else wav).contiguous()
+        if w.dtype != torch.float32:
+            w = w.float()
+        B, S = w.shape
+        if lens is not None and not torch.is_tensor(lens):
+            lens = [int(n) for n in lens]
+            if len(lens) != B:
+                raise ValueError(f"{len(lens)} lengths for {B} rows")
+            for n in lens:
+                if not 0 <= n <= S:
+                    raise ValueError(f"length {n}: 0..{S} samples")
+            lens = torch.from_numpy(np.asarray(lens, np.int64)).pin_memory().to(w.device,
+                                                                                 non_blocking=True)
+        out = K.f0_yin(w, lens, self.hop, self.sr, self.f0_floor, self.f0_ceil, self.threshold)
+        return tuple(o[0] for o in out) if single else out

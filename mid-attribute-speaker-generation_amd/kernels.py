@@ -816,6 +816,87 @@ def melspec(wav, lens, hop, window, twiddle, fb, n_mels, clip=False, energy=True
     return mel_o, en_o, mag_o, nf_o
 
 
+def _rows_f32(name, x, n):
+    _dev(x, n)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise RuntimeError(f"{name}: values are f32 (B, cols)")
+    if n is not None and (n.dtype != torch.int64 or n.numel() != x.shape[0]):
+        raise RuntimeError(f"{name}: the live counts are int64 (B)")
+
+
+def f0_yin(wav, lens, hop, sr, f0_floor=71.0, f0_ceil=800.0, threshold=0.15, out=None):
+    """The YIN F0 contour of a ragged batch (fs2_f0_yin): wav (B, S) f32, lens device int64 (B) or
+    None -> ``(f0 (B, F), dip (B, F), n_frames (B) int64)``, F = 1 + S // hop, zeros at frames
+    past ``n_frames``.  ``out`` = preallocated ``(f0, dip, n_frames)``."""
+    _rows_f32("f0_yin", wav, lens)
+    B, S = wav.shape
+    hop = int(hop)
+    if not 1 <= hop <= 1024:
+        raise RuntimeError(f"f0_yin: hop {hop} (1..1024)")
+    F, dev = 1 + S // hop, wav.device
+    if out is None:
+        out = (torch.empty((B, F), dtype=torch.float32, device=dev),
+               torch.empty((B, F), dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int64, device=dev))
+    f0, dip, nf = out
+    _dev(f0, dip, nf)
+    if f0.dtype != torch.float32 or dip.dtype != torch.float32 or f0.numel() != B * F or \
+            dip.numel() != B * F or nf.dtype != torch.int64 or nf.numel() != B:
+        raise RuntimeError("f0_yin: out is (f0 (B, F), dip (B, F)) f32 and n_frames (B) int64")
+    lib.fs2_f0_yin(ptr(wav), ptr(lens), B, S, hop, float(sr), float(f0_floor), float(f0_ceil),
+                   float(threshold), ptr(f0), ptr(dip), ptr(nf), stream())
+    return f0, dip, nf
+
+
+def pitch_fill_(x, n=None):
+    """Interpolate over the zero frames of each row in place (fs2_pitch_fill,
+    preprocessor.py:213-221): x (B, F) f32, n device int64 (B) live frames or None ->
+    ``ok (B) int32``, 1 where the row has more than one non-zero frame (others are untouched)."""
+    _rows_f32("pitch_fill", x, n)
+    ok = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+    lib.fs2_pitch_fill(ptr(x), ptr(n), x.shape[0], x.shape[1], ptr(ok), stream())
+    return ok
+
+
+def segment_mean_(x, durations, n=None):
+    """Phoneme-level means (fs2_segment_mean, preprocessor.py:223-242): x (B, F) f32, durations
+    (B, P) int64, n device int64 (B) live frames or None -> (B, P) f32.  As in the reference the
+    means are also written over ``x[:, :P]`` while later phonemes still read it."""
+    _rows_f32("segment_mean", x, n)
+    _dev(durations)
+    if durations.dim() != 2 or durations.dtype != torch.int64 or durations.shape[0] != x.shape[0]:
+        raise RuntimeError("segment_mean: durations are int64 (B, P)")
+    out = torch.empty(durations.shape, dtype=torch.float32, device=x.device)
+    lib.fs2_segment_mean(ptr(x), ptr(n), ptr(durations), x.shape[0], x.shape[1],
+                         durations.shape[1], ptr(out), stream())
+    return out
+
+
+def outlier_moments_(state, sorted_values, n=None):
+    """state (device f64[3] = count, mean, M2) takes in, row by row, the values of
+    ``sorted_values`` (B, cols) f32 (ascending, the ``n[b]`` live ones first) that survive
+    ``remove_outlier`` (fs2_outlier_moments, preprocessor.py:307-315 and 94-97)."""
+    _rows_f32("outlier_moments", sorted_values, n)
+    _dev(state)
+    if state.dtype != torch.float64 or state.numel() != 3:
+        raise RuntimeError("outlier_moments: state is f64[3]")
+    lib.fs2_outlier_moments(ptr(sorted_values), ptr(n), sorted_values.shape[0],
+                            sorted_values.shape[1], ptr(state), stream())
+    return state
+
+
+def normalize_minmax_(x, mean, std, minmax, n=None):
+    """x[b, :n[b]] = (x - mean) / std in place; minmax (device f64[2]) keeps the running
+    extrema of the stored values (fs2_normalize_minmax, preprocessor.py:317-328)."""
+    _rows_f32("normalize_minmax", x, n)
+    _dev(minmax)
+    if minmax.dtype != torch.float64 or minmax.numel() != 2:
+        raise RuntimeError("normalize_minmax: minmax is f64[2]")
+    lib.fs2_normalize_minmax(ptr(x), ptr(n), x.shape[0], x.shape[1], float(mean), float(std),
+                             ptr(minmax), stream())
+    return x
+
+
 def ge2e_eer(enroll, verify):
     """test()'s scoring of one batch: enroll (N, M_e, D), verify (N, M_v, D) ->
     sim (N, M_v, N), table (50, 2) = FAR, FRR per threshold, result (4) = EER, threshold, FAR,
