@@ -854,9 +854,11 @@ int fs2_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const
 /* torch.optim.Adam with coupled L2 weight decay (train_speech_embedder.py:104-113):
  * g <- norm_coef[1] g + weight_decay p (clip first), then Adam.  step (device int64[1]) is the
  * optimiser's step count, hyper (device float[3]) scratch.  gate (device float, nullable):
- * with gate[0] == 0 nothing changes, step included -- torch's "no parameter has a gradient". */
+ * with gate[0] == 0 nothing changes, step included -- torch's "no parameter has a gradient".
+ * The betas are doubles, as torch's: 1 - beta is formed in double and then rounded (1.f -
+ * 0.999f is 1.3e-5 off 0.001f, which went straight into v).                            */
 int fs2_adam_l2_step(float* p, const float* g, float* m, float* v, int64_t n,
-                     const float* norm_coef, float lr, float beta1, float beta2, float eps,
+                     const float* norm_coef, float lr, double beta1, double beta2, float eps,
                      float weight_decay, int64_t* step, float* hyper, const float* gate,
                      void* stream);
 /* out[0] = x[0] < threshold ? 1 : 0 (a device-side condition for the gates above)      */

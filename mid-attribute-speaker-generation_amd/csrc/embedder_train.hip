@@ -307,6 +307,8 @@ __global__ __launch_bounds__(64 * GE_WAVES) void ge2e_softmax_kernel(Ge2e a) {
 // torch.optim.Adam(weight_decay = wd): g <- clip_coef g + wd p, then Adam.  The step counter
 // lives on the device; with a gate (device float) of 0 the call is torch's "no parameter has a
 // gradient": nothing moves, the counter included.  hyper = [1 - b1^t, sqrt(1 - b2^t), on].
+// omb1 / omb2 are 1 - beta formed in double on the host and rounded once, as torch rounds its
+// scalars: 1.f - 0.999f is 0.00099998713, 1.3e-5 short of 0.001f, and v would carry that.
 __global__ void adam_l2_tick(int64_t* step, float* hyper, double b1, double b2, const float* gate) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const bool on = !gate || gate[0] != 0.f;
@@ -318,16 +320,17 @@ __global__ void adam_l2_tick(int64_t* step, float* hyper, double b1, double b2, 
 
 __global__ void adam_l2_kernel(float* __restrict__ p, const float* __restrict__ g,
                                float* __restrict__ m, float* __restrict__ v, int64_t n,
-                               const float* __restrict__ norm_coef, float lr, float b1, float b2,
-                               float eps, float wd, const float* __restrict__ hyper) {
+                               const float* __restrict__ norm_coef, float lr, float omb1,
+                               float b2, float omb2, float eps, float wd,
+                               const float* __restrict__ hyper) {
   if (hyper[2] == 0.f) return;
   const float coef = norm_coef ? norm_coef[1] : 1.f;
   const float step = lr / hyper[0], bc2s = hyper[1];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float pv = p[i], gv = fmaf(wd, pv, g[i] * coef);
-    const float mv = m[i] + (gv - m[i]) * (1.f - b1);
-    const float vv = b2 * v[i] + (1.f - b2) * gv * gv;
+    const float mv = m[i] + (gv - m[i]) * omb1;
+    const float vv = b2 * v[i] + omb2 * gv * gv;
     m[i] = mv;
     v[i] = vv;
     p[i] = pv - step * mv / (sqrtf(vv) / bc2s + eps);
@@ -399,19 +402,21 @@ int fs2_ge2e_softmax(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim
 }
 
 int fs2_adam_l2_step(float* p, const float* g, float* m, float* v, int64_t n,
-                     const float* norm_coef, float lr, float beta1, float beta2, float eps,
+                     const float* norm_coef, float lr, double beta1, double beta2, float eps,
                      float weight_decay, int64_t* step, float* hyper, const float* gate,
                      void* stream) {
   FS2_CHECK_ARG(p && g && m && v && step && hyper, "fs2_adam_l2_step: missing operand");
   FS2_CHECK_ARG(n >= 0 && weight_decay >= 0.f, "fs2_adam_l2_step: n %lld, weight_decay %g",
                 (long long)n, (double)weight_decay);
   hipStream_t st = as_stream(stream);
-  adam_l2_tick<<<1, 64, 0, st>>>(step, hyper, (double)beta1, (double)beta2, gate);
+  adam_l2_tick<<<1, 64, 0, st>>>(step, hyper, beta1, beta2, gate);
   if (n > 0) {
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    adam_l2_kernel<<<(unsigned)blocks, 256, 0, st>>>(p, g, m, v, n, norm_coef, lr, beta1, beta2,
-                                                     eps, weight_decay, hyper);
+    adam_l2_kernel<<<(unsigned)blocks, 256, 0, st>>>(p, g, m, v, n, norm_coef, lr,
+                                                     (float)(1.0 - beta1), (float)beta2,
+                                                     (float)(1.0 - beta2), eps, weight_decay,
+                                                     hyper);
   }
   return launch_status("fs2_adam_l2_step");
 }

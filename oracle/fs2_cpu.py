@@ -307,9 +307,12 @@ class GMMParams:
     def __init__(self, pi, mu, sigma):
         self.pi, self.mu, self.sigma = pi, mu, sigma
 
-    def log_prob(self, e):
+    def log_prob(self, e, eps=None):
+        """``eps``: the probability clamp; None is the tensors' own (torch.distributions).  A
+        float64 evaluation passes float32's to stay a reference for the float32 model."""
         probs = self.pi / self.pi.sum(-1, keepdim=True)
-        eps = torch.finfo(probs.dtype).eps
+        if eps is None:
+            eps = torch.finfo(probs.dtype).eps
         logits = torch.log(probs.clamp(min=eps, max=1 - eps))
         log_mix = torch.log_softmax(logits, dim=-1)
         x = e[:, None, :]
