@@ -324,6 +324,26 @@ int fs2_melspec(const float* wav, const int64_t* lens, int64_t batch, int64_t sa
 int fs2_f0_yin(const float* wav, const int64_t* lens, int64_t batch, int64_t samples, int64_t hop,
                double sr, double f0_floor, double f0_ceil, double threshold, float* f0, float* dip,
                int64_t* n_frames, void* stream);
+/* Rational polyphase FIR resampling of a ragged batch, where preprocessor/preprocessor.py:186
+ * calls librosa.load(sr=22050) (no parity with resampy's interpolated filter table is claimed).
+ * wav (batch, samples) fp32, lens (device int64, nullable = samples; read clamped into
+ * [0, samples]); up = L and down = M coprime (sr_out / gcd, sr_in / gcd); table (2 half + 1)
+ * fp32 = L h[i], h the low-pass filter centred at i = half (audio.resample_filter).  Per row,
+ * n_out = ceil(len L / M) and
+ *   y[n] = sum_j table[n M + half - j L] x[j],  0 <= n < n_out,
+ * over the j in [0, len) whose table index lies in [0, 2 half], j ascending, one fp32
+ * accumulator, every product rounded before it is added (no fused multiply-add).  Nothing past
+ * len is read.  out_first, out_count (device int64, nullable = 0 and everything after
+ * out_first; read clamped into [0, n_out] and [0, min(n_out - first, out_samples)]) select a
+ * window: out (batch, out_samples) fp32 receives y[first + n] for n < count and zeros after,
+ * out_lens (batch) int64 the count.  A sample's value depends on its row's samples only: not
+ * on the batch, the window or the call.  samples < 2^30; batch * ceil(out_samples / 256) <
+ * 2^31 suffices (a tile is 256 outputs or more); the sample span of 256 outputs
+ * (255 M / L + 2 half / L + 3) at most 12 288.                                             */
+int fs2_resample(const float* wav, const int64_t* lens, int64_t batch, int64_t samples,
+                 const float* table, int64_t table_len, int64_t up, int64_t down, int64_t half,
+                 const int64_t* out_first, const int64_t* out_count, float* out,
+                 int64_t out_samples, int64_t* out_lens, void* stream);
 /* preprocessor.py:213-221 in place: per row of x (batch, frames) fp32 with n[b] live frames
  * (device int64, nullable = frames; clamped into [0, frames]), every zero frame becomes the
  * line between its non-zero neighbours (fp64, rounded once), the first non-zero value before

@@ -224,3 +224,98 @@ class PitchExtractor:
                                                                                  non_blocking=True)
         out = K.f0_yin(w, lens, self.hop, self.sr, self.f0_floor, self.f0_ceil, self.threshold)
         return tuple(o[0] for o in out) if single else out
+
+
+# ------------------------------------------------------------------ resampling
+KAISER_ROLLOFF, KAISER_BETA = 0.9475937167399596, 14.769656459379492  # resampy's kaiser_best
+
+
+def resample_filter(sr_in, sr_out, zeros=64):
+    """The low-pass filter of a rational resampler ``sr_in -> sr_out`` as ``fs2_resample`` reads
+    it: ``(table float32 (2 half + 1), L, M, half)`` with ``L / M = sr_out / sr_in`` in lowest
+    terms, ``half = ceil(zeros max(L, M) / rolloff)`` and ``table[i] = L h[i]``,
+
+      h[i] = (rolloff / big) sinc(rolloff t / big) I0(beta sqrt(1 - (t / half)^2)) / I0(beta),
+      t = i - half, big = max(L, M),
+
+    a Kaiser-windowed sinc with the design numbers of resampy's ``kaiser_best``; computed in
+    fp64 and rounded once."""
+    sr_in, sr_out = int(sr_in), int(sr_out)
+    if sr_in < 1 or sr_out < 1 or zeros < 1:
+        raise ValueError(f"rates {sr_in} -> {sr_out}, zeros {zeros}")
+    g = int(np.gcd(sr_in, sr_out))
+    L, M = sr_out // g, sr_in // g
+    big = max(L, M)
+    half = int(np.ceil(zeros * big / KAISER_ROLLOFF))
+    t = np.arange(-half, half + 1, dtype=np.float64)
+    window = np.i0(KAISER_BETA * np.sqrt(np.maximum(1.0 - (t / half) ** 2, 0.0))) / np.i0(KAISER_BETA)
+    h = (KAISER_ROLLOFF / big) * np.sinc(KAISER_ROLLOFF * t / big) * window
+    return (L * h).astype(np.float32), L, M, half
+
+
+class Resampler:
+    """Waveforms of any rate at ``sr_out`` (``fs2_resample``), where the reference calls
+    ``librosa.load(wav_path, sr=22050)`` (preprocessor.py:186).  librosa 0.7.2 resamples with
+    resampy's ``kaiser_best``, which interpolates a 512-point table of a Kaiser-windowed sinc;
+    this is a polyphase FIR that evaluates the same window design exactly at the offsets the
+    ratio needs.  It is another implementation and its sample values are not resampy's (nor
+    soxr's); no parity is claimed.  The device tables are kept per ``sr_in``."""
+
+    def __init__(self, sr_out=22050, device="cuda", zeros=64):
+        self.sr_out, self.zeros = int(sr_out), int(zeros)
+        self.device = torch.device(device)
+        self._tables = {}
+
+    def table(self, sr_in):
+        sr_in = int(sr_in)
+        if sr_in not in self._tables:
+            tab, L, M, half = resample_filter(sr_in, self.sr_out, self.zeros)
+            self._tables[sr_in] = (torch.from_numpy(tab).to(self.device), L, M, half)
+        return self._tables[sr_in]
+
+    def out_len(self, length, sr_in):
+        """``ceil(length L / M)``: the samples a row of ``length`` gives."""
+        _, L, M, _ = self.table(sr_in) if int(sr_in) != self.sr_out else (None, 1, 1, 0)
+        return -(-int(length) * L // M)
+
+    def _i64(self, values, B, name):
+        if values is None or torch.is_tensor(values):
+            return values
+        values = [int(v) for v in values]
+        if len(values) != B:
+            raise ValueError(f"{len(values)} {name} values for {B} rows")
+        return torch.from_numpy(np.asarray(values, np.int64)).pin_memory().to(self.device,
+                                                                              non_blocking=True)
+
+    def __call__(self, wav, lens, sr_in, first=None, count=None):
+        """wav (B, S) f32 on the device -> ``(out (B, S_out), out_lens (B) int64)``, zeros past
+        ``out_lens``.  ``lens``: None (S each), a host list (checked) or a device int64 tensor
+        (not read back).  ``first`` / ``count`` (per row, host lists or device int64) cut the
+        window ``y[first:first + count]`` out of each row's result, the reference's trim
+        (lines 187-189) at no cost; S_out is the largest ``count`` of a host list, otherwise
+        ``ceil(S L / M)``.  Equal rates launch nothing: the input comes back (and ``lens`` as a
+        tensor), and a window is then not supported."""
+        if wav.dim() != 2:
+            raise ValueError("wav is (B, S)")
+        w = wav.contiguous()
+        if w.dtype != torch.float32:
+            w = w.float()
+        B, S = w.shape
+        if lens is not None and not torch.is_tensor(lens):
+            lens = [int(n) for n in lens]
+            for n in lens:
+                if not 0 <= n <= S:
+                    raise ValueError(f"length {n}: 0..{S} samples")
+        if int(sr_in) == self.sr_out:
+            if first is not None or count is not None:
+                raise ValueError("equal rates: nothing is launched, slice the rows instead")
+            if lens is None:
+                lens = torch.full((B,), S, dtype=torch.int64, device=w.device)
+            return wav, self._i64(lens, B, "lens")
+        tab, L, M, half = self.table(sr_in)
+        cols = -(-S * L // M)
+        if count is not None and not torch.is_tensor(count):
+            cols = max(min(max(int(c) for c in count), cols), 1)
+        return K.resample(w, self._i64(lens, B, "lens"), tab, L, M, half,
+                          first=self._i64(first, B, "first"), count=self._i64(count, B, "count"),
+                          out_samples=cols)

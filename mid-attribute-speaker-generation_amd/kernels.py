@@ -848,6 +848,38 @@ def f0_yin(wav, lens, hop, sr, f0_floor=71.0, f0_ceil=800.0, threshold=0.15, out
     return f0, dip, nf
 
 
+def resample(wav, lens, table, up, down, half, first=None, count=None, out_samples=None, out=None):
+    """Rational polyphase resampling of a ragged batch (fs2_resample): wav (B, S) f32, lens
+    device int64 (B) or None, table device f32 (2 half + 1) = L h (audio.resample_filter),
+    up = L, down = M -> ``(out (B, out_samples), out_lens (B) int64)``, zeros past ``out_lens``.
+    ``first`` / ``count`` (device int64 (B) or None) select the window ``y[first:first + count]``
+    of each row; ``out_samples`` defaults to ``ceil(S L / M)``.  ``out`` = preallocated
+    ``(out, out_lens)``."""
+    _rows_f32("resample", wav, lens)
+    _dev(table, first, count)
+    if table.dtype != torch.float32 or table.dim() != 1:
+        raise RuntimeError("resample: table is f32 (2 half + 1)")
+    B, S = wav.shape
+    for name, v in (("first", first), ("count", count)):
+        if v is not None and (v.dtype != torch.int64 or v.numel() != B):
+            raise RuntimeError(f"resample: {name} is int64 (B)")
+    up, down, half = int(up), int(down), int(half)
+    if up < 1 or down < 1:
+        raise RuntimeError(f"resample: L {up}, M {down}")
+    if out is None:
+        cols = -(-S * up // down) if out_samples is None else int(out_samples)
+        out = (torch.empty((B, max(cols, 1)), dtype=torch.float32, device=wav.device),
+               torch.empty(B, dtype=torch.int64, device=wav.device))
+    y, n = out
+    _dev(y, n)
+    if y.dtype != torch.float32 or y.dim() != 2 or y.shape[0] != B or not y.is_contiguous() or \
+            n.dtype != torch.int64 or n.numel() != B:
+        raise RuntimeError("resample: out is (out (B, out_samples) f32, out_lens (B) int64)")
+    lib.fs2_resample(ptr(wav), ptr(lens), B, S, ptr(table), table.numel(), up, down, half,
+                     ptr(first), ptr(count), ptr(y), y.shape[1], ptr(n), stream())
+    return y, n
+
+
 def pitch_fill_(x, n=None):
     """Interpolate over the zero frames of each row in place (fs2_pitch_fill,
     preprocessor.py:213-221): x (B, F) f32, n device int64 (B) live frames or None ->

@@ -2,8 +2,11 @@
 on the device: a waveform and its alignment give the mel, pitch, energy and duration targets that
 ``dataset.py`` loads, and a corpus of them gives ``stats.json``.
 
-  get_alignment       267-305   ``durations_from_intervals`` (host; TextGrid parsing stays with
-                                the caller, who hands over ``(start, end, text)`` tuples)
+  build_from_path     61-167    ``Preprocessor`` (the walk over ``raw_path``, ``.wav`` and
+                                TextGrid reading by ``corpus_io``, resampling by
+                                ``audio.Resampler``, the ``.npy`` files, ``stats.json``, the split)
+  get_alignment       267-305   ``durations_from_intervals`` (host, over ``(start, end, text)``
+                                tuples such as ``corpus_io.read_textgrid`` returns)
   process_utterance   169-265   ``FeatureExtractor`` (batched, device tensors) and its
                                 ``process_utterance`` (one numpy waveform, numpy results)
   remove_outlier, StandardScaler.partial_fit, normalize, stats.json
@@ -17,14 +20,21 @@ Quirk kept: the phoneme-level average writes ``pitch[i]`` while later phonemes s
 same array (lines 224-231); after zero durations ``pos`` falls behind ``i`` and a later phoneme
 averages means already written.  ``fs2_segment_mean`` reproduces it.
 """
+import json
+import os
+import random
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import torch
 
 from . import kernels as K
-from .audio import MelFrontEnd, N_FFT, PitchExtractor, frame_count
+from .audio import MelFrontEnd, N_FFT, PitchExtractor, Resampler, frame_count
 from .config import load_configs
+from .corpus_io import read_textgrid, read_wav
 
 SIL_PHONES = ("sil", "sp", "spn", "silB", "silE", "")
+DECODE_THREADS = 4  # file reading and PCM decoding of a group; not sized by the machine
 
 
 def durations_from_intervals(intervals, sr, hop):
@@ -223,3 +233,279 @@ class CorpusStats:
             self.finalize()
         lo, hi = self.minmax.cpu().tolist()
         return [float(lo), float(hi), float(self.mean), float(self.std)]
+
+
+class Preprocessor:
+    """The reference's class (preprocessor/preprocessor.py:16-167), same constructor argument
+    and ``build_from_path()``: ``raw_path/<speaker>/<basename>.wav`` + ``.lab`` and
+    ``preprocessed_path/TextGrid/<speaker>/<basename>.TextGrid`` become ``mel/ pitch/ energy/
+    duration/`` ``.npy`` files, ``stats.json`` and ``train.txt`` / ``val.txt`` / ``test.txt``.
+
+    ``config`` is the reference's merged dict (``path.raw_path``, ``path.preprocessed_path``,
+    ``preprocessing.{val_size, test_size, audio, stft, mel, pitch, energy}``).  Utterances are
+    taken ``batch`` at a time: decoded on the host (``corpus_io.read_wav``, a small thread pool),
+    packed into one pinned buffer and copied once, resampled on the device with one launch per
+    distinct file rate (``audio.Resampler``, the trim of lines 187-189 as its output window), and
+    put through ``FeatureExtractor`` in one call.  Pitch and energy stay on the device between the
+    two passes while they fit ``keep_bytes`` (then every file is written once, normalised);
+    past the budget a group's raw values go to their files and the second pass re-reads them.
+    Only the files this run wrote are normalised.
+
+    Differences from the reference, all deliberate: speakers and files are walked in sorted
+    order (``os.listdir`` order there) and the split is drawn from ``random.Random(seed)``; the
+    F0 contour is ``audio.PitchExtractor``'s unless ``f0_dir`` holds
+    ``<speaker>-f0-<basename>.npy`` contours of the trimmed waveforms; pitch and energy are
+    stored as float32."""
+
+    def __init__(self, config, device="cuda", batch=16, seed=None, f0_dir=None,
+                 keep_bytes=1 << 30):
+        self.config = config
+        self.in_dir = config["path"]["raw_path"]
+        self.out_dir = config["path"]["preprocessed_path"]
+        pp = config["preprocessing"]
+        self.val_size, self.test_size = pp["val_size"], pp["test_size"]
+        self.sampling_rate = pp["audio"]["sampling_rate"]
+        self.hop_length = pp["stft"]["hop_length"]
+        self.pitch_normalization = pp["pitch"]["normalization"]
+        self.energy_normalization = pp["energy"]["normalization"]
+        self.device = torch.device(device)
+        self.batch, self.seed, self.f0_dir = int(batch), seed, f0_dir
+        self.keep_bytes = int(keep_bytes)
+        if self.batch < 1:
+            raise ValueError(f"batch {batch}")
+        self.extractor = FeatureExtractor(pp, device)  # checks pitch.feature / energy.feature
+        self.pitch_phoneme_averaging = self.extractor.pitch_phoneme
+        self.energy_phoneme_averaging = self.extractor.energy_phoneme
+        self.resampler = Resampler(self.sampling_rate, device)
+        self._pinned = None
+
+    # -------------------------------------------------------------- the walk (lines 74-92)
+    def _walk(self):
+        """``[(speaker index, speaker, basename, phones, durations, start, end)]`` of the
+        utterances to process and the sorted speakers; a missing TextGrid raises (line 92)."""
+        speakers = sorted(s for s in os.listdir(self.in_dir)
+                          if os.path.isdir(os.path.join(self.in_dir, s)))
+        items = []
+        for si, speaker in enumerate(speakers):
+            for wav_name in sorted(os.listdir(os.path.join(self.in_dir, speaker))):
+                if ".wav" not in wav_name:
+                    continue
+                basename = wav_name.split(".")[0]
+                tg_path = os.path.join(self.out_dir, "TextGrid", speaker, f"{basename}.TextGrid")
+                if not os.path.exists(tg_path):
+                    raise ValueError(tg_path)
+                tiers = read_textgrid(tg_path)
+                if "phones" not in tiers:
+                    raise ValueError(f"{tg_path}: no interval tier named 'phones'")
+                phones, durations, start, end = durations_from_intervals(
+                    tiers["phones"], self.sampling_rate, self.hop_length)
+                if start >= end:
+                    continue
+                items.append((si, speaker, basename, phones, durations, start, end))
+        return speakers, items
+
+    def _stage(self, group, pool):
+        """One group's waveforms at the configured rate, trimmed: ``(wavs (B, S) on the device,
+        lens)``.  The decoded files go through one pinned buffer and one copy; each distinct file
+        rate is one ``(rows, samples)`` block of it and one resample launch."""
+        sr_out = self.sampling_rate
+        paths = [os.path.join(self.in_dir, it[1], f"{it[2]}.wav") for it in group]
+        decoded = list(pool.map(read_wav, paths))
+        window = [(int(sr_out * it[5]), int(sr_out * it[6])) for it in group]
+        by_rate = {}
+        for b, (x, sr) in enumerate(decoded):
+            by_rate.setdefault(sr, []).append(b)
+        rows = {}
+        for sr, members in by_rate.items():
+            if sr == sr_out:  # nothing to resample: only the trimmed span is copied
+                for b in members:
+                    rows[b] = decoded[b][0][window[b][0]:window[b][1]]
+            else:
+                for b in members:
+                    rows[b] = decoded[b][0]
+        blocks, total = {}, 0
+        for sr, members in by_rate.items():
+            S = max(max(len(rows[b]) for b in members), 1)
+            blocks[sr] = (total, S)
+            total += len(members) * S
+        if self._pinned is None or self._pinned.numel() < total:
+            self._pinned = torch.empty(max(total, 1 << 20), dtype=torch.float32).pin_memory()
+        host = self._pinned.numpy()
+        for sr, members in by_rate.items():
+            off, S = blocks[sr]
+            for k, b in enumerate(members):
+                n = len(rows[b])
+                host[off + k * S:off + k * S + n] = rows[b]
+                host[off + k * S + n:off + (k + 1) * S] = 0.0
+        dev = self._pinned[:total].to(self.device, non_blocking=True)
+        parts, lens = {}, [0] * len(group)
+        for sr, members in by_rate.items():
+            off, S = blocks[sr]
+            block = dev[off:off + len(members) * S].view(len(members), S)
+            n_in = [len(rows[b]) for b in members]
+            if sr == sr_out:
+                out, n_out = block, n_in
+            else:
+                first = [window[b][0] for b in members]
+                count = [max(window[b][1] - window[b][0], 0) for b in members]
+                out, _ = self.resampler(block, n_in, sr, first=first, count=count)
+                n_out = [max(min(c, self.resampler.out_len(n, sr) - f), 0)
+                         for n, f, c in zip(n_in, first, count)]
+            parts[sr] = out
+            for k, b in enumerate(members):
+                lens[b] = n_out[k]
+        if len(parts) == 1:
+            (wavs,) = parts.values()
+            return wavs[:, :max(max(lens), 1)].contiguous(), lens
+        wavs = torch.zeros((len(group), max(max(lens), 1)), dtype=torch.float32, device=self.device)
+        for sr, members in by_rate.items():
+            out = parts[sr]
+            wavs[torch.as_tensor(members, device=self.device), :out.shape[1]] = out[:, :wavs.shape[1]]
+        return wavs, lens
+
+    def _given_f0(self, group, totals):
+        T = max(max(totals), 1)
+        f0 = np.zeros((len(group), T), np.float32)
+        for b, it in enumerate(group):
+            c = np.load(os.path.join(self.f0_dir, f"{it[1]}-f0-{it[2]}.npy")).astype(np.float32)
+            f0[b, :min(len(c), T)] = c[:T]
+        return f0
+
+    def _path(self, kind, speaker, basename):
+        return os.path.join(self.out_dir, kind, f"{speaker}-{kind}-{basename}.npy")
+
+    def build_from_path(self):
+        for kind in ("mel", "pitch", "energy", "duration"):
+            os.makedirs(os.path.join(self.out_dir, kind), exist_ok=True)
+        print("Processing Data ...")
+        speakers, items = self._walk()
+        out = [[] for _ in speakers]
+        stats = {"pitch": CorpusStats(self.device, self.pitch_normalization),
+                 "energy": CorpusStats(self.device, self.energy_normalization)}
+        phoneme = {"pitch": self.pitch_phoneme_averaging, "energy": self.energy_phoneme_averaging}
+        kept, kept_bytes, n_frames = [], 0, 0
+        fx = self.extractor
+        with ThreadPoolExecutor(max_workers=DECODE_THREADS) as pool:
+            for g0 in range(0, len(items), self.batch):
+                group = items[g0:g0 + self.batch]
+                wavs, lens = self._stage(group, pool)
+                durations = [it[4] for it in group]
+                totals = []
+                for it, n in zip(group, lens):
+                    try:
+                        totals.append(check_utterance(n, it[4], self.hop_length,
+                                                      fx.pitch_phoneme or fx.energy_phoneme))
+                    except ValueError as err:
+                        raise ValueError(f"{it[2]}: {err}") from None
+                f0 = self._given_f0(group, totals) if self.f0_dir is not None else None
+                res = fx(wavs, lens, durations, f0=f0)
+                ok = res["ok"].cpu().numpy() != 0  # line 204: the one host read of a group
+                rows = np.flatnonzero(ok)
+                if rows.size == 0:
+                    continue
+                pick = torch.from_numpy(rows).to(self.device)
+                mel = res["mel"].index_select(0, pick).cpu().numpy()
+                members = [group[b] for b in rows]
+                for k, (si, speaker, basename, phones, dur, _, _) in enumerate(members):
+                    np.save(self._path("duration", speaker, basename), np.asarray(dur, np.int64))
+                    np.save(self._path("mel", speaker, basename), mel[k, :sum(dur)])
+                    with open(os.path.join(self.in_dir, speaker, f"{basename}.lab"), "r") as f:
+                        raw_text = f.readline().strip("\n")
+                    out[si].append("|".join([basename, speaker, "{" + " ".join(phones) + "}",
+                                             raw_text]))
+                    n_frames += sum(dur)
+                entry = {"members": members}
+                for name in ("pitch", "energy"):
+                    values = res[name].index_select(0, pick).contiguous()
+                    n = res["n_phones" if phoneme[name] else "n_frames"].index_select(0, pick)
+                    stats[name].partial_fit(values, n)
+                    entry[name] = (values, n)
+                    kept_bytes += values.numel() * 4
+                if kept_bytes > self.keep_bytes:  # past the budget: raw values to the files
+                    for name in ("pitch", "energy"):
+                        self._write(name, members, *entry[name])
+                        entry[name] = None
+                kept.append(entry)
+
+        print("Computing statistic quantities ...")
+        for entry in kept:
+            for name in ("pitch", "energy"):
+                if entry[name] is None:
+                    entry[name] = self._reread(name, entry["members"])
+                values, n = entry[name]
+                stats[name].normalize_(values, n)
+                self._write(name, entry["members"], values, n)
+        with open(os.path.join(self.out_dir, "stats.json"), "w") as f:
+            f.write(json.dumps({"pitch": stats["pitch"].stats() if kept else [0.0, 0.0, 0.0, 1.0],
+                                "energy": stats["energy"].stats() if kept else [0.0, 0.0, 0.0, 1.0]}))
+        print("Total time: {} hours".format(n_frames * self.hop_length / self.sampling_rate / 3600))
+        write_split(out, self.out_dir, self.val_size, self.test_size, self.seed)
+        return out
+
+    def _write(self, name, members, values, n):
+        values, n = values.cpu().numpy(), n.cpu().tolist()
+        for k, (_, speaker, basename, *_) in enumerate(members):
+            np.save(self._path(name, speaker, basename), values[k, :n[k]])
+
+    def _reread(self, name, members):
+        rows = [np.load(self._path(name, it[1], it[2])) for it in members]
+        values = np.zeros((len(rows), max(max(len(r) for r in rows), 1)), np.float32)
+        for k, r in enumerate(rows):
+            values[k, :len(r)] = r
+        n = torch.from_numpy(np.asarray([len(r) for r in rows], np.int64)).to(self.device)
+        return torch.from_numpy(values).to(self.device), n
+
+
+def write_split(out, out_dir, val_size, test_size, seed=None):
+    """Lines 149-165 with a generator of its own: ``out`` (one list of metadata lines per
+    speaker) is shuffled in place, speakers first and then each speaker's lines, and every
+    speaker's lines are cut at ``int(len * (1 - val - test))`` and ``int(len * (1 - test))`` into
+    ``train.txt``, ``val.txt`` and ``test.txt``."""
+    rng = random.Random(seed)
+    rng.shuffle(out)
+    for r in out:
+        rng.shuffle(r)
+    cuts = {"train.txt": lambda n: (0, int(n * (1 - val_size - test_size))),
+            "val.txt": lambda n: (int(n * (1 - val_size - test_size)), int(n * (1 - test_size))),
+            "test.txt": lambda n: (int(n * (1 - test_size)), n)}
+    for name, cut in cuts.items():
+        with open(os.path.join(out_dir, name), "w", encoding="utf-8") as f:
+            for spk in out:
+                lo, hi = cut(len(spk))
+                for m in spk[lo:hi]:
+                    f.write(m + "\n")
+    return out
+
+
+def main(argv=None):
+    """The reference's ``preprocess.py``: ``--config DIR [--corpus NAME]`` reads
+    ``DIR/preprocess.yaml`` (with its two ``normalization = False`` overrides) and
+    ``DIR/preprocess_<corpus>.yaml``, every ``preprocess_*.yaml`` without ``--corpus``."""
+    import argparse
+    from pathlib import Path
+
+    import yaml
+
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--config", type=str, required=True, help="path to config")
+    parser.add_argument("--corpus", type=str, default=None, help="corpus name")
+    args = parser.parse_args(argv)
+    with open(os.path.join(args.config, "preprocess.yaml")) as f:
+        preprocess_config = yaml.safe_load(f)
+    preprocess_config["pitch"]["normalization"] = False
+    preprocess_config["energy"]["normalization"] = False
+    if args.corpus is not None:
+        files = [Path(args.config) / f"preprocess_{args.corpus}.yaml"]
+    else:
+        files = sorted(Path(args.config).glob("preprocess_*.yaml"))
+    for path in files:
+        with open(path) as f:
+            config = yaml.safe_load(f)
+        config["preprocessing"] = preprocess_config
+        config["preprocessing"]["text"] = config["text"]
+        print("preprocessing...:", config["dataset"])
+        Preprocessor(config).build_from_path()
+
+
+if __name__ == "__main__":
+    main()
