@@ -344,6 +344,54 @@ int fs2_resample(const float* wav, const int64_t* lens, int64_t batch, int64_t s
                  const float* table, int64_t table_len, int64_t up, int64_t down, int64_t half,
                  const int64_t* out_first, const int64_t* out_count, float* out,
                  int64_t out_samples, int64_t* out_lens, void* stream);
+/* librosa.effects.split of a ragged batch (Multilingual-Speaker-Encoder-with-Domain-Adaptation/
+ * data_preprocess.py:46; the rule is librosa 0.7.2's, read from its source, nothing was compared
+ * with it).  wav (batch, samples) fp32, lens (device int64, nullable = samples; read clamped
+ * into [0, samples]); frame_length even in 2..4096, 1 <= hop <= frame_length.  Per row, frames
+ * f < n_f = 1 + len / hop (0 for len = 0); frame f covers the padded samples
+ * f hop - frame_length / 2 .. + frame_length - 1.  pad_mode 0 is reflect padding (librosa
+ * 0.7.2's rms) by the index rule of fs2_melspec: index -k is k, len - 1 + k is len - 1 - k, every
+ * index clamped into [0, len - 1] -- numpy's reflect for len > frame_length / 2, a stated
+ * deviation for shorter rows; pad_mode 1 is zero padding (librosa >= 0.10).
+ *   p_f   = (sum of the frame's squares) / frame_length: fp32, each square rounded once (no
+ *           fused multiply-add), 64 interleaved partial sums (sample i in partial i mod 64,
+ *           ascending) joined by a fixed butterfly, so p_f depends on the frame's samples only
+ *   p_max = max_f p_f
+ *   frame f is non-silent iff max(1e-10, p_f) > max(1e-10, p_max) 10^(-top_db / 10), in fp64:
+ *           10 log10(max(1e-10, p_f)) - 10 log10(max(1e-10, p_max)) > -top_db
+ * The maximal runs [f0, f1) of non-silent frames, in order, are the intervals
+ * [min(f0 hop, len), min(f1 hop, len)].  n_intervals (batch) int32 receives the true count;
+ * intervals (batch, max_intervals, 2) int64 the first max_intervals of them and ZEROS after the
+ * count.  power (batch, F_max = 1 + samples / hop) fp32, nullable, receives p_f and zeros at
+ * f >= n_f; without it ws (fs2_nonsilent_split_ws_bytes) holds the powers, with it ws may be
+ * NULL.  At top_db = 100 every row with |x| < 1 is the single interval [0, len].  samples <
+ * 2^30.  A row's result does not depend on its place in the batch.                          */
+int64_t fs2_nonsilent_split_ws_bytes(int64_t batch, int64_t samples, int64_t hop);
+int fs2_nonsilent_split(const float* wav, const int64_t* lens, int64_t batch, int64_t samples,
+                        int64_t frame_length, int64_t hop, double top_db, int pad_mode,
+                        int64_t* intervals, int64_t max_intervals, int32_t* n_intervals,
+                        float* power, float* ws, int64_t ws_bytes, void* stream);
+/* Intervals as rows for fs2_melspec (data_preprocess.py:56):
+ *   out[s, i] = wav[seg_row[s], seg_first[s] + i], i < seg_len[s], and 0 up to out_samples.
+ * wav (batch, samples) fp32; the descriptors are device int32 / int64 / int64, one per segment;
+ * the caller guarantees seg_first + seg_len <= samples and seg_len <= out_samples (they are
+ * read clamped to that, so a broken descriptor reads nothing outside wav).  out (n_seg,
+ * out_samples) fp32.  n_seg = 0 launches nothing.                                          */
+int fs2_wave_segments(const float* wav, int64_t batch, int64_t samples, const int32_t* seg_row,
+                      const int64_t* seg_first, const int64_t* seg_len, int64_t n_seg, float* out,
+                      int64_t out_samples, void* stream);
+/* The half-overlapping windows of data_preprocess.py:63-66.  mel (rows, n_mels, frames) fp32 as
+ * fs2_melspec writes it, n_frames (rows) device int64 (read clamped into [0, frames]).  Row r
+ * with F = n_frames[r] yields the windows j = 0, 1, ... while 2 F >= tisv (j + 2):
+ * mel[r, :, s_j : s_j + tisv], s_j = floor(tisv j / 2) -- the reference's float loop
+ * `i += 0.5; int(tisv * i)` in integers, floor(2 F / tisv) - 1 windows for F >= tisv, else none.
+ * win_off (rows + 1) device int64: the exclusive prefix of those counts, from the host (which
+ * knows every F); n_windows = win_off[rows].  out (n_windows, n_mels, tisv) fp32; a window the
+ * offsets promise and the row lacks is written as zeros.  tisv <= 256, n_mels <= 128;
+ * n_windows = 0 launches nothing.                                                          */
+int fs2_tisv_windows(const float* mel, const int64_t* n_frames, int64_t rows, int64_t n_mels,
+                     int64_t frames, int64_t tisv, const int64_t* win_off, int64_t n_windows,
+                     float* out, void* stream);
 /* preprocessor.py:213-221 in place: per row of x (batch, frames) fp32 with n[b] live frames
  * (device int64, nullable = frames; clamped into [0, frames]), every zero frame becomes the
  * line between its non-zero neighbours (fp64, rounded once), the first non-zero value before

@@ -13,6 +13,10 @@ They are the same arithmetic: periodic Hann window of 1024, hop 256, centred fra
 padding of 512, the magnitude of the 513 bins, the Slaney mel filterbank (80 filters, 0-8000 Hz at
 22 050 Hz, area normalised) and ``log(clamp(., 1e-5))``.  Everything on the host here is table
 construction (fp64, rounded to fp32); the arithmetic on samples runs in the kernel.
+
+Beside it: ``PitchExtractor`` (YIN F0 on the same frames), ``SilenceSplitter``
+(``librosa.effects.split``, the speaker encoder's data_preprocess.py:46) and ``Resampler``
+(``librosa.load``'s rate conversion).
 """
 import numpy as np
 import torch
@@ -224,6 +228,73 @@ class PitchExtractor:
                                                                                  non_blocking=True)
         out = K.f0_yin(w, lens, self.hop, self.sr, self.f0_floor, self.f0_ceil, self.threshold)
         return tuple(o[0] for o in out) if single else out
+
+
+# ------------------------------------------------------------------ silence split
+class SilenceSplitter:
+    """``librosa.effects.split(y, top_db, frame_length=2048, hop_length=512)`` on the device
+    (``fs2_nonsilent_split``): the intervals of samples whose frames lie within ``top_db`` dB of
+    the row's loudest frame (mean-square power per centred frame, floor 1e-10).  The rule is
+    librosa 0.7.2's, read from its source; librosa is not a dependency and nothing was compared
+    with it.  ``pad_mode="reflect"`` is that version's framing, ``"zero"`` librosa >= 0.10's.
+
+    At ``top_db = 100`` -- the value data_preprocess.py:46 passes -- a waveform in (-1, 1) has
+    ``p_max < 1``, every frame lies above ``p_max 1e-10 < 1e-10 <= max(1e-10, p_f)`` and the
+    result is the single interval ``[0, len]``."""
+
+    PAD_MODES = {"reflect": 0, "zero": 1}
+
+    def __init__(self, top_db=60.0, frame_length=2048, hop_length=512, pad_mode="reflect",
+                 device="cuda"):
+        self.top_db, self.frame_length, self.hop = float(top_db), int(frame_length), int(hop_length)
+        if pad_mode not in self.PAD_MODES:
+            raise ValueError(f"pad_mode {pad_mode!r}: one of {sorted(self.PAD_MODES)}")
+        if self.frame_length < 2 or self.frame_length > 4096 or self.frame_length % 2:
+            raise ValueError(f"frame_length {frame_length} (even, 2..4096)")
+        if not 1 <= self.hop <= self.frame_length:
+            raise ValueError(f"hop_length {hop_length} (1..{self.frame_length})")
+        if self.top_db != self.top_db:
+            raise ValueError("top_db is NaN")
+        self.pad_mode = pad_mode
+        self.device = torch.device(device)
+
+    def n_frames(self, length):
+        return frame_count(length, self.hop) if int(length) > 0 else 0
+
+    def __call__(self, wav, lens=None, max_intervals=None):
+        """wav (B, S) or (S,) on the device -> ``(intervals (B, max_intervals, 2) int64,
+        n_intervals (B) int32)`` on the device (without the batch axis for a 1-D wav).
+        ``n_intervals`` is the true count, so ``n_intervals > max_intervals`` shows an overflow;
+        rows of ``intervals`` past the count are zero.  ``max_intervals`` defaults to the bound
+        ``(1 + S // hop) // 2 + 1``.  ``lens``: None (S for every row), a host list (checked) or
+        a device int64 tensor (not read back).  An empty row has no interval."""
+        single = wav.dim() == 1
+        w = (wav[None] if single else wav).contiguous()
+        if w.dtype != torch.float32:
+            w = w.float()
+        B, S = w.shape
+        if lens is not None and not torch.is_tensor(lens):
+            lens = [int(n) for n in lens]
+            if len(lens) != B:
+                raise ValueError(f"{len(lens)} lengths for {B} rows")
+            for n in lens:
+                if not 0 <= n <= S:
+                    raise ValueError(f"length {n}: 0..{S} samples")
+            lens = torch.from_numpy(np.asarray(lens, np.int64)).pin_memory().to(w.device,
+                                                                                 non_blocking=True)
+        iv, n_iv, _ = K.nonsilent_split(w, lens, self.top_db, self.frame_length, self.hop,
+                                        self.PAD_MODES[self.pad_mode], max_intervals)
+        return (iv[0], n_iv[0]) if single else (iv, n_iv)
+
+    def split(self, y):
+        """A numpy waveform -> numpy ``(n, 2)`` int64 intervals, the shape of the librosa call."""
+        y = np.ascontiguousarray(y, np.float32)
+        if y.ndim != 1:
+            raise ValueError("split takes one mono waveform")
+        if y.size == 0:
+            return np.zeros((0, 2), np.int64)
+        iv, n = self(torch.from_numpy(y).to(self.device))
+        return iv[:int(n)].cpu().numpy()
 
 
 # ------------------------------------------------------------------ resampling

@@ -880,6 +880,99 @@ def resample(wav, lens, table, up, down, half, first=None, count=None, out_sampl
     return y, n
 
 
+def nonsilent_split(wav, lens, top_db, frame_length=2048, hop=512, pad_mode=0, max_intervals=None,
+                    power=False, out=None):
+    """``librosa.effects.split`` of a ragged batch (fs2_nonsilent_split): wav (B, S) f32, lens
+    device int64 (B) or None -> ``(intervals (B, max_intervals, 2) int64, n_intervals (B) int32,
+    power (B, F) f32 or None)``, F = 1 + S // hop.  ``n_intervals`` is the true count, entries
+    of ``intervals`` past it are zero; ``max_intervals`` defaults to the bound ``F // 2 + 1``.
+    ``pad_mode`` 0 reflects, 1 pads zeros.  ``out`` = preallocated
+    ``(intervals, n_intervals, power or None)``."""
+    _rows_f32("nonsilent_split", wav, lens)
+    B, S = wav.shape
+    frame_length, hop = int(frame_length), int(hop)
+    if frame_length < 2 or frame_length > 4096 or frame_length % 2 or not 1 <= hop <= frame_length:
+        raise RuntimeError(f"nonsilent_split: frame_length {frame_length} (even, 2..4096), "
+                           f"hop {hop} (1..frame_length)")
+    if S < 1:
+        raise RuntimeError("nonsilent_split: wav has no samples")
+    F, dev = 1 + S // hop, wav.device
+    if out is None:
+        cap = F // 2 + 1 if max_intervals is None else int(max_intervals)
+        out = (torch.empty((B, cap, 2), dtype=torch.int64, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty((B, F), dtype=torch.float32, device=dev) if power else None)
+    iv, n_iv, pw = out
+    _dev(iv, n_iv, pw)
+    if iv.dtype != torch.int64 or iv.dim() != 3 or iv.shape[0] != B or iv.shape[2] != 2 or \
+            n_iv.dtype != torch.int32 or n_iv.numel() != B or \
+            (pw is not None and (pw.dtype != torch.float32 or pw.numel() != B * F)):
+        raise RuntimeError("nonsilent_split: out is (intervals (B, max_intervals, 2) int64, "
+                           "n_intervals (B) int32, power (B, F) f32 or None)")
+    nbytes = 0 if pw is not None else lib.fs2_nonsilent_split_ws_bytes(B, S, hop)
+    scratch = ws(nbytes, dev) if pw is None else None
+    lib.fs2_nonsilent_split(ptr(wav), ptr(lens), B, S, frame_length, hop, float(top_db),
+                            int(pad_mode), ptr(iv), iv.shape[1], ptr(n_iv), ptr(pw), ptr(scratch),
+                            nbytes, stream())
+    return iv, n_iv, pw
+
+
+def wave_segments(wav, seg_row, seg_first, seg_len, out_samples, out=None):
+    """out[s, i] = wav[seg_row[s], seg_first[s] + i] for i < seg_len[s], zeros up to
+    ``out_samples`` (fs2_wave_segments): wav (B, S) f32; descriptors device int32 / int64 /
+    int64, one per segment; the caller guarantees ``seg_first + seg_len <= S`` and
+    ``seg_len <= out_samples``."""
+    _dev(wav, seg_row, seg_first, seg_len, out)
+    if wav.dim() != 2 or wav.dtype != torch.float32:
+        raise RuntimeError("wave_segments: wav is f32 (B, S)")
+    if (seg_row.dtype, seg_first.dtype, seg_len.dtype) != (torch.int32, torch.int64, torch.int64):
+        raise RuntimeError("wave_segments: seg_row i32, seg_first / seg_len i64")
+    n = seg_row.numel()
+    if seg_first.numel() != n or seg_len.numel() != n:
+        raise RuntimeError("wave_segments: one descriptor of each kind per segment")
+    out_samples = int(out_samples)
+    if out_samples < 1 or wav.numel() == 0:
+        raise RuntimeError(f"wave_segments: out_samples {out_samples}, wav {tuple(wav.shape)}")
+    if out is None:
+        out = torch.empty((n, out_samples), dtype=torch.float32, device=wav.device)
+    elif out.dtype != torch.float32 or out.numel() != n * out_samples:
+        raise RuntimeError("wave_segments: out is f32 (n_seg, out_samples)")
+    lib.fs2_wave_segments(ptr(wav), wav.shape[0], wav.shape[1], ptr(seg_row), ptr(seg_first),
+                          ptr(seg_len), n, ptr(out), out_samples, stream())
+    return out
+
+
+def tisv_window_count(frames, tisv):
+    """Windows of ``tisv`` frames at half-window steps in ``frames`` frames
+    (data_preprocess.py:63-66): ``2 frames // tisv - 1``, 0 below ``tisv``."""
+    frames, tisv = int(frames), int(tisv)
+    return 2 * frames // tisv - 1 if frames >= tisv else 0
+
+
+def tisv_windows(mel, n_frames, win_off, n_windows, tisv, out=None):
+    """The half-overlapping ``tisv``-frame windows of each row of mel (rows, n_mels, F) f32
+    (fs2_tisv_windows): window j of row r is ``mel[r, :, tisv j // 2 : tisv j // 2 + tisv]``.
+    n_frames device int64 (rows); win_off device int64 (rows + 1), the exclusive prefix of
+    ``tisv_window_count`` per row, and ``n_windows`` its last entry (both from the host) ->
+    (n_windows, n_mels, tisv)."""
+    _dev(mel, n_frames, win_off, out)
+    if mel.dim() != 3 or mel.dtype != torch.float32:
+        raise RuntimeError("tisv_windows: mel is f32 (rows, n_mels, F)")
+    rows, n_mels, F = mel.shape
+    if n_frames.dtype != torch.int64 or n_frames.numel() != rows or \
+            win_off.dtype != torch.int64 or win_off.numel() != rows + 1:
+        raise RuntimeError("tisv_windows: n_frames int64 (rows), win_off int64 (rows + 1)")
+    n_windows, tisv = int(n_windows), int(tisv)
+    if out is None:
+        out = torch.empty((n_windows, n_mels, tisv), dtype=torch.float32, device=mel.device)
+    elif out.dtype != torch.float32 or out.numel() != n_windows * n_mels * tisv:
+        raise RuntimeError("tisv_windows: out is f32 (n_windows, n_mels, tisv)")
+    if n_windows:
+        lib.fs2_tisv_windows(ptr(mel), ptr(n_frames), rows, n_mels, F, tisv, ptr(win_off),
+                             n_windows, ptr(out), stream())
+    return out
+
+
 def pitch_fill_(x, n=None):
     """Interpolate over the zero frames of each row in place (fs2_pitch_fill,
     preprocessor.py:213-221): x (B, F) f32, n device int64 (B) live frames or None ->
