@@ -305,6 +305,49 @@ int fs2_melspec(const float* wav, const int64_t* lens, int64_t batch, int64_t sa
                 const int32_t* fb_first, const int32_t* fb_count, const int32_t* fb_off,
                 const float* fb_w, int64_t n_weights, int64_t n_mels, int clip, int log_mag,
                 float* mel, float* energy, float* mag, int64_t* n_frames, void* stream);
+/* Griffin-Lim (common/audio_processing.py:86-102 over STFT.inverse, common/stft.py:107-137, and
+ * TacotronSTFT._mel_to_linear, common/layers.py:125-131): the inverse half of fs2_melspec's
+ * transform pair.  Built for n_fft = win_length = 1024 (513 bins) and 128 <= hop <= 512; anything
+ * else is an argument error.  Ragged convention: n_frames (batch) device int64, nullable =
+ * frames, read clamped into [0, frames]; row b has F_b live frames and L_b = hop (F_b - 1)
+ * samples (0 for F_b <= 1); waveforms are (batch, hop (frames - 1)) fp32 and everything past L_b
+ * is written as exact zeros.  A row's result depends on that row's data only and is bitwise
+ * batch invariant (no atomics, fixed summation orders).  Nothing allocates or synchronises.
+ *
+ * fs2_mel_to_linear: mel (batch, n_mels, frames) holds LOG-mels,
+ *   mag[b, k, f] = max(sum_m inv_basis[k, m] exp(mel[b, m, f]), 1e-10),
+ * one fp32 accumulator, m ascending; inv_basis (513, n_mels) fp32 (audio.inverse_mel_basis);
+ * mag (batch, 513, frames), zeros at f >= F_b.  n_mels <= 128.
+ *
+ * fs2_istft: mag and phase (nullable = zero phase) are (batch, 513, frames); window (1024) and
+ * twiddle (1024, 2) as fs2_melspec takes them.  With p the position before the trim,
+ *   y[p]   = sum_f w[p - f hop] irfft_1024(mag[:, f] e^(i phase[:, f]))[p - f hop]
+ *            / sum_f w^2[p - f hop],
+ * both sums over the frames f < F_b that cover p, f ascending, and wav[t] = y[t + 512] for
+ * t < L_b.  The irfft uses only the real parts of bins 0 and 512.  The reference's inverse basis
+ * pinv(scale fourier_basis) is this irfft times hop / n_fft and its later factor n_fft / hop
+ * cancels that; both are dropped.  Its `window_sum > tiny` exception is not made: for
+ * 128 <= hop <= 512 every kept position is covered by a frame at an offset with w^2 > 0 (the
+ * periodic Hann window vanishes at offset 0 only), so the divisor is positive throughout.
+ *
+ * fs2_griffin_lim_step: one pass of the loop body (audio_processing.py:100-101).  Per live frame
+ * the span of wav_in is taken by fs2_melspec's index rule (reflection against L_b), windowed and
+ * transformed to X[k]; X'[k] = mag[k] X[k] / |X[k]|, and (mag[k], 0) where |X[k]| = 0 (the
+ * reference's atan2(0, 0) = 0); then the inverse transform, the window and the overlap-add of
+ * fs2_istft.  wav_out must not overlap wav_in.
+ *
+ * ws (fs2_griffin_lim_ws_bytes: (batch, frames, 1024) fp32) is the caller's and receives the
+ * windowed inverse frames; a second launch sums them per sample.  batch = 0 launches nothing. */
+int fs2_mel_to_linear(const float* mel, const int64_t* n_frames, int64_t batch, int64_t n_mels,
+                      int64_t frames, const float* inv_basis, float* mag, void* stream);
+int64_t fs2_griffin_lim_ws_bytes(int64_t batch, int64_t frames);
+int fs2_istft(const float* mag, const float* phase, const int64_t* n_frames, int64_t batch,
+              int64_t frames, int64_t n_fft, int64_t hop, const float* window,
+              const float* twiddle, float* wav, float* ws, int64_t ws_bytes, void* stream);
+int fs2_griffin_lim_step(const float* wav_in, const float* mag, const int64_t* n_frames,
+                         int64_t batch, int64_t frames, int64_t n_fft, int64_t hop,
+                         const float* window, const float* twiddle, float* wav_out, float* ws,
+                         int64_t ws_bytes, void* stream);
 /* The F0 contour of a ragged batch by YIN (de Cheveigne & Kawahara 2002), the estimator that
  * stands where preprocessor/preprocessor.py:196-201 calls pyworld (no parity with DIO is
  * claimed).  wav (batch, samples) fp32, lens (device int64, nullable = samples; read clamped

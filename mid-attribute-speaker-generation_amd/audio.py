@@ -14,6 +14,10 @@ padding of 512, the magnitude of the 513 bins, the Slaney mel filterbank (80 fil
 22 050 Hz, area normalised) and ``log(clamp(., 1e-5))``.  Everything on the host here is table
 construction (fp64, rounded to fp32); the arithmetic on samples runs in the kernel.
 
+``GriffinLim`` is the way back (``TacotronSTFT.inv_mel_spectrogram`` / ``inv_linear_spectrogram``,
+common/layers.py:125-141): mel inversion, inverse STFT and the Griffin-Lim loop on the same
+tables, and a ``forward_rows`` that stands in for the vocoder where no checkpoint exists.
+
 Beside it: ``PitchExtractor`` (YIN F0 on the same frames), ``SilenceSplitter``
 (``librosa.effects.split``, the speaker encoder's data_preprocess.py:46) and ``Resampler``
 (``librosa.load``'s rate conversion).
@@ -179,6 +183,130 @@ class MelFrontEnd:
         """``TacotronSTFT.linear_spectrogram`` (layers.py:120-123): (B, T) -> (B, 513, F),
         ``log(clamp(|STFT|, 1e-5))``."""
         return self(y, log_mag=True)[3]
+
+
+def inverse_mel_basis(fb_dense):
+    """The (bins, n_mels) pseudo-inverse of a float32 filterbank (n_mels, bins), computed in
+    float64 and rounded once to float32.  ``TacotronSTFT._mel_to_linear`` (layers.py:125-131)
+    calls ``torch.pinverse`` in fp32 on every call; this is built once per ``GriffinLim``.  The
+    rows of the bins no filter reaches (above ``fmax``) are zero."""
+    fb = np.asarray(fb_dense, np.float32)
+    return np.ascontiguousarray(np.linalg.pinv(fb.astype(np.float64)).astype(np.float32))
+
+
+class GriffinLim:
+    """Audio without a vocoder checkpoint: ``TacotronSTFT.inv_mel_spectrogram`` /
+    ``inv_linear_spectrogram`` (layers.py:125-141) over ``griffin_lim``
+    (audio_processing.py:86-102) and ``STFT.inverse`` (stft.py:107-137), on the kernels
+    ``fs2_mel_to_linear``, ``fs2_istft`` and ``fs2_griffin_lim_step``.  The window, twiddle and
+    filterbank tables are those of a ``MelFrontEnd`` (``front_end``, or one built from
+    ``preprocess_config``).  ``128 <= hop_length <= 512``.
+
+    Ragged batches: ``n_frames`` is None (every frame), a host list or a device int64 tensor
+    (not read back).  A row of ``F`` frames gives ``hop (F - 1)`` samples -- the signal whose
+    centred STFT has ``F`` frames -- and zeros after them.
+
+    The initial phase is drawn on the device from ``generator`` (``self.generator`` when none is
+    passed; None = torch's default stream).  The reference draws it from numpy's global stream;
+    no parity with that stream is claimed.  ``forward_rows`` makes an instance a drop-in for the
+    vocoder argument of ``synthesize.synth_batch`` / ``synthesize`` / ``synth_dvectors``."""
+
+    def __init__(self, preprocess_config=None, device="cuda", n_iters=60, front_end=None):
+        self.front = front_end if front_end is not None else MelFrontEnd(preprocess_config, device)
+        self.hop, self.n_mels, self.device = self.front.hop, self.front.n_mels, self.front.device
+        if not 128 <= self.hop <= 512:
+            raise ValueError(f"hop_length {self.hop}: the inverse is built for 128..512")
+        self.n_iters = int(n_iters)
+        self.inv_mel_basis = inverse_mel_basis(self.front.mel_basis)
+        self.generator = None
+        self._inv = None
+
+    def _tables(self):
+        window, twiddle, _ = self.front._dev_tables()
+        if self._inv is None:
+            self._inv = torch.from_numpy(self.inv_mel_basis).to(self.device)
+        return window, twiddle, self._inv
+
+    def _spec(self, x, name):
+        if x.dim() != 3:
+            raise ValueError(f"{name} is (B, channels, frames)")
+        x = x.contiguous()
+        return x if x.dtype == torch.float32 else x.float()
+
+    def _counts(self, n_frames, B, F):
+        if n_frames is None:
+            return None
+        if torch.is_tensor(n_frames):
+            if n_frames.numel() != B:
+                raise ValueError(f"{n_frames.numel()} frame counts for {B} rows")
+            return n_frames.to(device=self.device, dtype=torch.int64).reshape(B).contiguous()
+        n = [int(v) for v in n_frames]
+        if len(n) != B or min(n) < 0 or max(n) > F:
+            raise ValueError(f"n_frames must be {B} frame counts in [0, {F}]")
+        return torch.from_numpy(np.asarray(n, np.int64)).pin_memory().to(self.device,
+                                                                          non_blocking=True)
+
+    def inverse(self, magnitude, phase=None, n_frames=None):
+        """``STFT.inverse``: magnitude, phase (None = zero) (B, 513, F) -> wav (B, hop (F - 1))."""
+        mag = self._spec(magnitude, "magnitude")
+        window, twiddle, _ = self._tables()
+        return K.istft(mag, None if phase is None else self._spec(phase, "phase"),
+                       self._counts(n_frames, mag.shape[0], mag.shape[2]), self.hop, window, twiddle)
+
+    def mel_to_linear(self, mel, n_frames=None):
+        """``_mel_to_linear`` of LOG-mels (B, n_mels, F): ``max(pinv(mel_basis) @ exp(mel),
+        1e-10)`` (B, 513, F)."""
+        mel = self._spec(mel, "mel")
+        return K.mel_to_linear(mel, self._counts(n_frames, mel.shape[0], mel.shape[2]),
+                               self._tables()[2])
+
+    def griffin_lim(self, magnitudes, n_iters=None, angles=None, n_frames=None, generator=None):
+        """``griffin_lim``: the inverse of ``magnitudes`` (B, 513, F) under ``angles`` (drawn
+        uniform in (-pi, pi] when None; given angles make the result deterministic), then
+        ``n_iters`` passes of transform / keep the phase / invert, two waveform buffers taking
+        turns and one frame workspace: ``2 (n_iters + 1)`` launches, nothing allocated between."""
+        mag = self._spec(magnitudes, "magnitudes")
+        B, _, F = mag.shape
+        n_iters = self.n_iters if n_iters is None else int(n_iters)
+        nf = self._counts(n_frames, B, F)
+        window, twiddle, _ = self._tables()
+        if angles is None:
+            gen = generator if generator is not None else self.generator
+            u = torch.rand(mag.shape, dtype=torch.float32, device=mag.device, generator=gen)
+            angles = float(np.pi) - (2.0 * float(np.pi)) * u
+        scratch = K.griffin_lim_ws(B, F, mag.device)
+        cur = K.istft(mag, self._spec(angles, "angles"), nf, self.hop, window, twiddle,
+                      ws_buf=scratch)
+        nxt = torch.empty_like(cur) if n_iters > 0 else None
+        for _ in range(n_iters):
+            K.griffin_lim_step(cur, mag, nf, self.hop, window, twiddle, out=nxt, ws_buf=scratch)
+            cur, nxt = nxt, cur
+        return cur
+
+    def inv_mel_spectrogram(self, mel, iter_=60, n_frames=None, generator=None, angles=None):
+        """``TacotronSTFT.inv_mel_spectrogram``: log-mel (B, n_mels, F) -> wav."""
+        return self.griffin_lim(self.mel_to_linear(mel, n_frames), iter_, angles, n_frames, generator)
+
+    def inv_linear_spectrogram(self, spec, iter_=60, n_frames=None, generator=None, angles=None):
+        """``TacotronSTFT.inv_linear_spectrogram``: log-magnitude (B, 513, F) -> wav."""
+        return self.griffin_lim(torch.exp(self._spec(spec, "spec")), iter_, angles, n_frames,
+                                generator)
+
+    @torch.no_grad()
+    def forward_rows(self, mel_rows, B, T, pcm=True, max_wav_value=32768.0, lengths=None):
+        """The contract of ``hifigan.Generator.forward_rows``: mel_rows (B*T, n_mels) (the
+        FastSpeech2 row layout) -> ``(wav (B*T*hop,) fp32, pcm int16 or None)``, ``lengths`` = mel
+        frames per utterance (a list or a device tensor such as the model's mel_len), ``n_iters``
+        passes.  Griffin-Lim yields ``hop (len - 1)`` samples: the last hop of each utterance
+        and everything after it is zeros.  int16 as ``fs2_vocoder_post`` converts: the product
+        with ``max_wav_value`` truncated toward zero, the low 16 bits kept."""
+        B, T = int(B), int(T)
+        mel = mel_rows.reshape(B, T, -1).transpose(1, 2)
+        live = self.inv_mel_spectrogram(mel, self.n_iters, n_frames=lengths)
+        wav = torch.zeros((B, T * self.hop), dtype=torch.float32, device=live.device)
+        wav[:, :live.shape[1]] = live
+        wav = wav.view(-1)
+        return wav, (wav * float(max_wav_value)).to(torch.int32).to(torch.int16) if pcm else None
 
 
 class PitchExtractor:

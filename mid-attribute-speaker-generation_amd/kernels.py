@@ -816,6 +816,104 @@ def melspec(wav, lens, hop, window, twiddle, fb, n_mels, clip=False, energy=True
     return mel_o, en_o, mag_o, nf_o
 
 
+def _spec_f32(name, bins, n_frames, *specs):
+    """(B, bins, frames) f32 operands (None allowed after the first) and the live counts."""
+    _dev(n_frames, *specs)
+    first = specs[0]
+    if first.dim() != 3 or first.shape[1] != bins:
+        raise RuntimeError(f"{name}: the spectrogram is f32 (B, {bins}, frames)")
+    for s in specs:
+        if s is not None and (s.dtype != torch.float32 or s.shape != first.shape):
+            raise RuntimeError(f"{name}: the spectrograms are f32 {tuple(first.shape)}")
+    if n_frames is not None and (n_frames.dtype != torch.int64 or n_frames.numel() != first.shape[0]):
+        raise RuntimeError(f"{name}: n_frames is int64 (B)")
+    if first.shape[2] < 1:
+        raise RuntimeError(f"{name}: no frames")
+    return first.shape[0], first.shape[2]
+
+
+def _tables_f32(name, window, twiddle):
+    _dev(window, twiddle)
+    if window.dtype != torch.float32 or window.numel() != 1024 or \
+            twiddle.dtype != torch.float32 or twiddle.numel() != 2048:
+        raise RuntimeError(f"{name}: window f32 (1024), twiddle f32 (1024, 2)")
+
+
+def griffin_lim_ws(batch, frames, device):
+    """The frame workspace of ``istft`` / ``griffin_lim_step`` (fs2_griffin_lim_ws_bytes)."""
+    return ws(lib.fs2_griffin_lim_ws_bytes(int(batch), int(frames)), device)
+
+
+def mel_to_linear(mel, n_frames, inv_basis, out=None):
+    """``TacotronSTFT._mel_to_linear`` on LOG-mels (fs2_mel_to_linear): mel (B, n_mels, F) f32,
+    n_frames device int64 (B) or None, inv_basis (513, n_mels) f32 ->
+    ``max(inv_basis @ exp(mel), 1e-10)`` (B, 513, F), zeros at frames past ``n_frames``."""
+    B, F = _spec_f32("mel_to_linear", mel.shape[1] if mel.dim() == 3 else -1, n_frames, mel)
+    _dev(inv_basis, out)
+    n_mels = mel.shape[1]
+    if inv_basis.dtype != torch.float32 or tuple(inv_basis.shape) != (513, n_mels):
+        raise RuntimeError(f"mel_to_linear: inv_basis is f32 (513, {n_mels})")
+    if out is None:
+        out = torch.empty((B, 513, F), dtype=torch.float32, device=mel.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 513, F):
+        raise RuntimeError("mel_to_linear: out is f32 (B, 513, F)")
+    lib.fs2_mel_to_linear(ptr(mel), ptr(n_frames), B, n_mels, F, ptr(inv_basis), ptr(out), stream())
+    return out
+
+
+def _wav_out(name, out, B, F, hop, dev):
+    cols = max(hop, 0) * (F - 1)
+    if out is None:
+        return torch.empty((B, cols), dtype=torch.float32, device=dev)
+    _dev(out)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, cols):
+        raise RuntimeError(f"{name}: the waveform is f32 (B, hop (frames - 1)) = ({B}, {cols})")
+    return out
+
+
+def _gl_ws(name, ws_buf, B, F, dev):
+    n = lib.fs2_griffin_lim_ws_bytes(B, F)
+    if ws_buf is None:
+        return ws(n, dev), n
+    _dev(ws_buf)
+    if ws_buf.dtype != torch.float32 or ws_buf.numel() * 4 < n:
+        raise RuntimeError(f"{name}: the workspace is f32 of {n} bytes (griffin_lim_ws)")
+    return ws_buf, ws_buf.numel() * 4
+
+
+def istft(mag, phase, n_frames, hop, window, twiddle, n_fft=1024, out=None, ws_buf=None):
+    """``STFT.inverse`` of a ragged batch (fs2_istft): mag, phase (None = zero phase)
+    (B, 513, F) f32, n_frames device int64 (B) or None -> wav (B, hop (F - 1)) f32, row b live
+    up to ``hop (n_frames[b] - 1)`` and zeros after.  ``window`` (1024), ``twiddle`` (1024, 2)
+    f32; ``ws_buf`` = a caller-owned ``griffin_lim_ws`` (else one is allocated)."""
+    B, F = _spec_f32("istft", 513, n_frames, mag, phase)
+    _tables_f32("istft", window, twiddle)
+    hop = int(hop)
+    wav = _wav_out("istft", out, B, F, hop, mag.device)
+    w, n = _gl_ws("istft", ws_buf, B, F, mag.device)
+    lib.fs2_istft(ptr(mag), ptr(phase), ptr(n_frames), B, F, int(n_fft), hop, ptr(window),
+                  ptr(twiddle), ptr(wav), ptr(w), n, stream())
+    return wav
+
+
+def griffin_lim_step(wav_in, mag, n_frames, hop, window, twiddle, n_fft=1024, out=None,
+                     ws_buf=None):
+    """One Griffin-Lim pass (fs2_griffin_lim_step): the STFT of wav_in (B, hop (F - 1)) f32, its
+    magnitudes replaced by ``mag`` (B, 513, F), inverted -> a new waveform of that shape.
+    ``out`` must not be ``wav_in``."""
+    B, F = _spec_f32("griffin_lim_step", 513, n_frames, mag)
+    _tables_f32("griffin_lim_step", window, twiddle)
+    hop = int(hop)
+    if wav_in is None:
+        raise RuntimeError("griffin_lim_step: wav_in is missing")
+    wav_in = _wav_out("griffin_lim_step", wav_in, B, F, hop, mag.device)
+    wav = _wav_out("griffin_lim_step", out, B, F, hop, mag.device)
+    w, n = _gl_ws("griffin_lim_step", ws_buf, B, F, mag.device)
+    lib.fs2_griffin_lim_step(ptr(wav_in), ptr(mag), ptr(n_frames), B, F, int(n_fft), hop,
+                             ptr(window), ptr(twiddle), ptr(wav), ptr(w), n, stream())
+    return wav
+
+
 def _rows_f32(name, x, n):
     _dev(x, n)
     if x.dim() != 2 or x.dtype != torch.float32:
