@@ -2,13 +2,12 @@
 // TacotronSTFT._mel_to_linear, common/layers.py:125-131): the inverse half of melspec.hip's
 // transform pair, n_fft = win = 1024, 128 <= hop <= 512, fp32 throughout.
 //
-// One iteration is two launches.  gl_frames_kernel: a block of 4 waves owns GL_FPB = 8
-// consecutive frames of one row, as melspec_kernel does.  It stages their sample span (melspec's
+// One iteration is two launches.  gl_frames_kernel: a block of 4 waves owns STFT_FPB = 8
+// consecutive frames of one row, as melspec_kernel does.  It stages their sample span (fft.hpp's
 // index rule, reflection against the row's own L = hop (F - 1)) and the (513, 8) tile of their
 // target magnitudes in LDS -- the global reads of the tile run along frames -- then each wave
 // takes two frames through
-//   window, forward 512-point complex FFT of z[n] = x[2n] + i x[2n + 1] (three radix-8 passes,
-//   melspec.hip's lane layout), real-input split -> X[k]
+//   the forward transform of fft.hpp (window, 512-point complex FFT, real-input split) -> X[k]
 //   X'[k] = mag[k] X[k] / |X[k]|   ((mag[k], 0) where |X[k]| = 0; no atan2 / sincos)
 //   inverse split  Z'[k] = E' + i O',  E' = (X'[k] + conj X'[512 - k]) / 2,
 //                  O' = W1024^-k (X'[k] - conj X'[512 - k]) / 2   (bins 0 and 512: real parts only)
@@ -28,9 +27,8 @@
 
 namespace fs2 {
 
-constexpr int GL_NFFT = 1024, GL_BINS = 513, GL_FPB = 8, GL_WAVES = 4, GL_EX = 576;
-constexpr int GL_TS = GL_FPB + 1;  // tile stride: bin k of frame j at 9 k + j (odd: spreads banks)
-constexpr int GL_TILE = GL_BINS * GL_TS;
+constexpr int GL_TS = STFT_FPB + 1;  // tile stride: bin k of frame j at 9 k + j (odd: spreads banks)
+constexpr int GL_TILE = STFT_BINS * GL_TS;
 constexpr int GL_HOP_MIN = 128, GL_HOP_MAX = 512;
 constexpr int GL_MELMAX = 128, GL_MFR = 64;  // fs2_mel_to_linear: frames per block
 constexpr int GL_MKP = 8;                    // ... and the blocks (grid y) that share its bins
@@ -54,58 +52,29 @@ FS2_DEV int live_frames(const int64_t* n_frames, int64_t b, int64_t frames) {
   return (int)nf;
 }
 
-// Forward 512-point FFT of one wave: in z[j] = x[64 j + lane], out z[q] = X[64 q + 8 lo + hi]
-// with lane = 8 hi + lo (the passes of melspec.hip).  ex_re / ex_im are the wave's own GL_EX
-// floats; the barriers are block wide, so every wave of the block calls this together.
-FS2_DEV void fft512(cpx* z, float* ex_re, float* ex_im, const cpx* tw1, const cpx* tw2, int lane,
-                    int hi, int lo) {
-  dft8(z);
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const cpx y = s ? cmul(z[s], tw1[s]) : z[s];
-    ex_re[72 * s + lane] = y.re;
-    ex_im[72 * s + lane] = y.im;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 8; ++q) z[q] = {ex_re[72 * hi + 8 * q + lo], ex_im[72 * hi + 8 * q + lo]};
-  __syncthreads();
-  dft8(z);
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const cpx y = t ? cmul(z[t], tw2[t]) : z[t];
-    ex_re[72 * hi + 9 * t + lo] = y.re;
-    ex_im[72 * hi + 9 * t + lo] = y.im;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 8; ++q) z[q] = {ex_re[72 * hi + 9 * lo + q], ex_im[72 * hi + 9 * lo + q]};
-  dft8(z);
-}
-
 // STEP: one Griffin-Lim pass from wav_in (else: the inverse of (mag, phase) alone)
 template <bool STEP>
-__global__ __launch_bounds__(64 * GL_WAVES) void gl_frames_kernel(GlFrames a) {
+__global__ __launch_bounds__(64 * STFT_WAVES) void gl_frames_kernel(GlFrames a) {
   extern __shared__ float smem[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int hop = a.hop;
   const int64_t b = blockIdx.x / a.chunks;
-  const int f0 = (int)(blockIdx.x - b * a.chunks) * GL_FPB;
+  const int f0 = (int)(blockIdx.x - b * a.chunks) * STFT_FPB;
   const int nf = live_frames(a.n_frames, b, a.frames);
   // a row of fewer than two frames has no sample, and no frame past nf is ever summed
   if (nf < 2 || f0 >= nf) return;  // block-uniform
   const int len = hop * (nf - 1);
-  const int live = nf - f0 < GL_FPB ? nf - f0 : GL_FPB;
-  const int span_n = (GL_FPB - 1) * hop + GL_NFFT;
+  const int live = nf - f0 < STFT_FPB ? nf - f0 : STFT_FPB;
+  const int span_n = (STFT_FPB - 1) * hop + STFT_NFFT;
 
   float* tile_a = smem;              // STEP: target magnitudes; else Re X'
   float* tile_b = tile_a + GL_TILE;  // STEP: the sample span; else Im X'
-  float* ex_re = tile_b + (STEP ? span_n : GL_TILE) + wave * 2 * GL_EX;
-  float* ex_im = ex_re + GL_EX;
+  float* ex_re = tile_b + (STEP ? span_n : GL_TILE) + wave * 2 * STFT_EX;
+  float* ex_im = ex_re + STFT_EX;
 
   {
-    const int64_t row = b * GL_BINS * a.frames + f0;
-    for (int i = tid; i < GL_BINS * GL_FPB; i += 64 * GL_WAVES) {
+    const int64_t row = b * STFT_BINS * a.frames + f0;
+    for (int i = tid; i < STFT_BINS * STFT_FPB; i += 64 * STFT_WAVES) {
       const int k = i >> 3, j = i & 7;
       float re = 0.f, im = 0.f;
       if (j < live) {  // the frames past nf hold anything: not read
@@ -123,70 +92,37 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gl_frames_kernel(GlFrames a) {
       if (!STEP) tile_b[k * GL_TS + j] = im;
     }
   }
-  if (STEP) {
-    const float* row = a.wav_in + b * a.S;
-    const int p0 = f0 * hop - GL_NFFT / 2;
-    for (int i = tid; i < span_n; i += 64 * GL_WAVES) {
-      int p = p0 + i;
-      p = p < 0 ? -p : p;
-      p = p > len - 1 ? 2 * (len - 1) - p : p;
-      p = p < 0 ? 0 : p > len - 1 ? len - 1 : p;
-      tile_b[i] = row[p];
-    }
-  }
+  if (STEP) stage_span(tile_b, a.wav_in + b * a.S, f0 * hop - STFT_NFFT / 2, span_n, len, tid, false);
 
   // frame-independent per-lane constants
   float win[16], winv[16];
-  cpx tw1[8], tw2[8], tws[8];
-  const int hi = lane >> 3, lo = lane & 7;  // (s, b) in pass 2, (s, t) in pass 3
-  const int m = 8 * lo + hi;                // low bin index of this lane after pass 3
+  LaneConst lc;
+  lane_consts(lc, a.twiddle, lane);
+  const int m = lc.m;
+  if (STEP) load_window(win, a.window, lane);
+  load_window(winv, a.window, m);  // the inverse's output sample pairs
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if (STEP) {
-      win[2 * j] = a.window[128 * j + 2 * lane];
-      win[2 * j + 1] = a.window[128 * j + 2 * lane + 1];
-    }
-    // the inverse's output sample pair 2 n, 2 n + 1 with n = 64 j + m; 1 / 512 is exact
-    winv[2 * j] = a.window[128 * j + 2 * m] * (1.f / 512.f);
-    winv[2 * j + 1] = a.window[128 * j + 2 * m + 1] * (1.f / 512.f);
-    const int i1 = 2 * lane * j, i2 = 16 * lo * j, i3 = 64 * j + m;
-    tw1[j] = {a.twiddle[2 * i1], a.twiddle[2 * i1 + 1]};
-    tw2[j] = {a.twiddle[2 * i2], a.twiddle[2 * i2 + 1]};
-    tws[j] = {a.twiddle[2 * i3], a.twiddle[2 * i3 + 1]};
-  }
-  const int mp = (64 - m) & 63;
-  const int partner = ((mp & 7) << 3) | (mp >> 3);
+  for (int j = 0; j < 16; ++j) winv[j] *= 1.f / 512.f;  // exact
   __syncthreads();
 
-  for (int it = 0; it < GL_FPB / GL_WAVES; ++it) {
-    const int jf = it * GL_WAVES + wave;  // frame within the block
+  for (int it = 0; it < STFT_FPB / STFT_WAVES; ++it) {
+    const int jf = it * STFT_WAVES + wave;  // frame within the block
     cpx z[8], xp[8];
     float x512;  // X'[512] (lane 0)
     if (STEP) {
-      const float* fr = tile_b + jf * hop;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int n2 = 128 * j + 2 * lane;
-        z[j] = {fr[n2] * win[2 * j], fr[n2 + 1] * win[2 * j + 1]};
-      }
-      fft512(z, ex_re, ex_im, tw1, tw2, lane, hi, lo);
-      // real-input split: X[k] = E + W1024^k O, E = (Z[k] + conj Z[512 - k]) / 2,
-      // O = -i (Z[k] - conj Z[512 - k]) / 2; then the target magnitude on X's direction
+      load_frame(z, tile_b + jf * hop, win, lane);
+      fft512(z, ex_re, ex_im, lc.tw1, lc.tw2, lane, lc.hi, lc.lo);
+      // the target magnitude on X's direction
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        cpx p = {__shfl(z[7 - q].re, partner, 64), __shfl(z[7 - q].im, partner, 64)};
-        if (lane == 0) p = z[(8 - q) & 7];
-        const float er = 0.5f * (z[q].re + p.re), ei = 0.5f * (z[q].im - p.im);
-        const float orr = 0.5f * (z[q].im + p.im), oi = -0.5f * (z[q].re - p.re);
-        const float xr = er + (tws[q].re * orr - tws[q].im * oi);
-        const float xi = ei + (tws[q].re * oi + tws[q].im * orr);
+        const cpx x = real_split(z, lc, lane, q);
         const float tg = tile_a[(64 * q + m) * GL_TS + jf];
-        const float mg = sqrtf(xr * xr + xi * xi);
+        const float mg = sqrtf(x.re * x.re + x.im * x.im);
         const float sc = tg / mg;
-        xp[q] = mg == 0.f ? cpx{tg, 0.f} : cpx{xr * sc, xi * sc};
+        xp[q] = mg == 0.f ? cpx{tg, 0.f} : cpx{x.re * sc, x.im * sc};
       }
-      // bin 512 = Re Z[0] - Im Z[0], real: its direction is its sign
-      const float v512 = z[0].re - z[0].im, tg512 = tile_a[512 * GL_TS + jf];
+      // bin 512 is real: its direction is its sign
+      const float v512 = real_split_512(z), tg512 = tile_a[512 * GL_TS + jf];
       x512 = v512 < 0.f ? -tg512 : tg512;
     } else {
 #pragma unroll
@@ -199,15 +135,15 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gl_frames_kernel(GlFrames a) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       cpx x = xp[q];
-      cpx p = {__shfl(xp[7 - q].re, partner, 64), __shfl(xp[7 - q].im, partner, 64)};
+      cpx p = {__shfl(xp[7 - q].re, lc.partner, 64), __shfl(xp[7 - q].im, lc.partner, 64)};
       if (lane == 0) {
         p = xp[(8 - q) & 7];
         if (q == 0) x.im = 0.f, p = {x512, 0.f};  // bins 0 and 512: their real parts only
       }
       const float er = 0.5f * (x.re + p.re), ei = 0.5f * (x.im - p.im);
       const float dr = 0.5f * (x.re - p.re), di = 0.5f * (x.im + p.im);
-      const float o_re = dr * tws[q].re + di * tws[q].im;  // (dr + i di) conj W1024^k
-      const float o_im = di * tws[q].re - dr * tws[q].im;
+      const float o_re = dr * lc.tws[q].re + di * lc.tws[q].im;  // (dr + i di) conj W1024^k
+      const float o_im = di * lc.tws[q].re - dr * lc.tws[q].im;
       z[q] = {er - o_im, -(ei + o_re)};  // conj(E' + i O')
     }
     __syncthreads();
@@ -220,9 +156,9 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gl_frames_kernel(GlFrames a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[j] = {ex_re[64 * j + lane], ex_im[64 * j + lane]};
     __syncthreads();
-    fft512(z, ex_re, ex_im, tw1, tw2, lane, hi, lo);
+    fft512(z, ex_re, ex_im, lc.tw1, lc.tw2, lane, lc.hi, lc.lo);
     if (jf < live) {
-      float* out = a.ws + (b * a.frames + f0 + jf) * GL_NFFT;
+      float* out = a.ws + (b * a.frames + f0 + jf) * STFT_NFFT;
 #pragma unroll
       for (int q = 0; q < 8; ++q)
         *reinterpret_cast<f32x2*>(out + 2 * (64 * q + m)) =
@@ -242,8 +178,8 @@ struct GlOla {
 };
 
 __global__ __launch_bounds__(256) void gl_ola_kernel(GlOla a) {
-  __shared__ float w2[GL_NFFT];
-  for (int i = threadIdx.x; i < GL_NFFT; i += 256) {
+  __shared__ float w2[STFT_NFFT];
+  for (int i = threadIdx.x; i < STFT_NFFT; i += 256) {
     const float w = a.window[i];
     w2[i] = w * w;
   }
@@ -253,20 +189,20 @@ __global__ __launch_bounds__(256) void gl_ola_kernel(GlOla a) {
   const int hop = a.hop;
   const int nf = live_frames(a.n_frames, b, a.frames);
   const int len = nf < 2 ? 0 : hop * (nf - 1);
-  const float* ws_b = a.ws + b * a.frames * GL_NFFT;
+  const float* ws_b = a.ws + b * a.frames * STFT_NFFT;
   float* out = a.wav + b * a.S;
   for (int i = threadIdx.x; i < GL_OLA; i += 256) {
     const int t = t0 + i;
     if (t >= a.S) break;
     float v = 0.f;
     if (t < len) {
-      const int p = t + GL_NFFT / 2;
-      const int f_lo = p < GL_NFFT ? 0 : (p - (GL_NFFT - 1) + hop - 1) / hop;
+      const int p = t + STFT_NFFT / 2;
+      const int f_lo = p < STFT_NFFT ? 0 : (p - (STFT_NFFT - 1) + hop - 1) / hop;
       const int f_hi = p / hop < nf - 1 ? p / hop : nf - 1;
       float acc = 0.f, den = 0.f;
       for (int f = f_lo; f <= f_hi; ++f) {
         const int o = p - f * hop;  // 0 .. 1023
-        acc += ws_b[(int64_t)f * GL_NFFT + o];
+        acc += ws_b[(int64_t)f * STFT_NFFT + o];
         den += w2[o];
       }
       v = acc / den;
@@ -292,9 +228,9 @@ __global__ __launch_bounds__(256) void mel_to_linear_kernel(const float* mel, co
   __syncthreads();
   const int64_t f = f0 + fj;
   if (f >= frames) return;
-  float* mag_b = mag + b * GL_BINS * frames + f;
+  float* mag_b = mag + b * STFT_BINS * frames + f;
   // k is wave-uniform: the basis row is broadcast
-  for (int k = 4 * blockIdx.y + kq; k < GL_BINS; k += 4 * GL_MKP) {
+  for (int k = 4 * blockIdx.y + kq; k < STFT_BINS; k += 4 * GL_MKP) {
     const float* pk = inv_basis + k * n_mels;
     float acc = 0.f;
     for (int c = 0; c < n_mels; ++c) acc = fmaf(pk[c], e[c * GL_MFR + fj], acc);
@@ -304,14 +240,14 @@ __global__ __launch_bounds__(256) void mel_to_linear_kernel(const float* mel, co
 
 // the argument checks fs2_istft and fs2_griffin_lim_step share
 static int gl_check(const char* fn, int64_t batch, int64_t frames, int64_t n_fft, int64_t hop) {
-  FS2_CHECK_ARG(n_fft == GL_NFFT, "%s: n_fft %lld (only n_fft = win_length = %d is built)", fn,
-                (long long)n_fft, GL_NFFT);
+  FS2_CHECK_ARG(n_fft == STFT_NFFT, "%s: n_fft %lld (only n_fft = win_length = %d is built)", fn,
+                (long long)n_fft, STFT_NFFT);
   FS2_CHECK_ARG(hop >= GL_HOP_MIN && hop <= GL_HOP_MAX, "%s: hop %lld (%d..%d)", fn, (long long)hop,
                 GL_HOP_MIN, GL_HOP_MAX);
   FS2_CHECK_ARG(batch >= 0, "%s: batch %lld", fn, (long long)batch);
   FS2_CHECK_ARG(frames >= 1 && hop * (frames - 1) < (1ll << 30), "%s: frames %lld (1.., samples < 2^30)",
                 fn, (long long)frames);
-  const int64_t chunks = (frames + GL_FPB - 1) / GL_FPB;
+  const int64_t chunks = (frames + STFT_FPB - 1) / STFT_FPB;
   FS2_CHECK_ARG(batch * chunks < (1ll << 31) && batch * frames < (1ll << 40),
                 "%s: batch %lld x %lld frames too large", fn, (long long)batch, (long long)frames);
   return FS2_OK;
@@ -329,16 +265,16 @@ static int gl_launch(const char* fn, bool step, const float* wav_in, const float
                 (long long)fs2_griffin_lim_ws_bytes(batch, frames));
   if (S == 0) return FS2_OK;  // one frame: no sample
   poison(ws, ws_bytes, st);
-  const int64_t chunks = (frames + GL_FPB - 1) / GL_FPB;
+  const int64_t chunks = (frames + STFT_FPB - 1) / STFT_FPB;
   GlFrames a{wav_in, mag, phase, n_frames, frames, S, (int)hop, (int)chunks, window, twiddle, ws};
   const dim3 grid((unsigned)(batch * chunks));
-  const size_t ex = sizeof(float) * GL_WAVES * 2 * GL_EX;
+  const size_t ex = sizeof(float) * STFT_WAVES * 2 * STFT_EX;
   if (step)
-    gl_frames_kernel<true><<<grid, 64 * GL_WAVES,
-                             sizeof(float) * (GL_TILE + (GL_FPB - 1) * (size_t)hop + GL_NFFT) + ex,
+    gl_frames_kernel<true><<<grid, 64 * STFT_WAVES,
+                             sizeof(float) * (GL_TILE + (STFT_FPB - 1) * (size_t)hop + STFT_NFFT) + ex,
                              st>>>(a);
   else
-    gl_frames_kernel<false><<<grid, 64 * GL_WAVES, sizeof(float) * 2 * GL_TILE + ex, st>>>(a);
+    gl_frames_kernel<false><<<grid, 64 * STFT_WAVES, sizeof(float) * 2 * GL_TILE + ex, st>>>(a);
   const int64_t tiles = (S + GL_OLA - 1) / GL_OLA;
   GlOla o{ws, n_frames, frames, S, (int)hop, (int)tiles, window, wav};
   gl_ola_kernel<<<dim3((unsigned)(batch * tiles)), 256, 0, st>>>(o);
@@ -371,7 +307,7 @@ int fs2_mel_to_linear(const float* mel, const int64_t* n_frames, int64_t batch, 
 
 int64_t fs2_griffin_lim_ws_bytes(int64_t batch, int64_t frames) {
   if (batch < 1 || frames < 1) return 0;
-  return batch * frames * GL_NFFT * (int64_t)sizeof(float);
+  return batch * frames * STFT_NFFT * (int64_t)sizeof(float);
 }
 
 int fs2_istft(const float* mag, const float* phase, const int64_t* n_frames, int64_t batch,

@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "fft.hpp"  // reflect_index only: no float arithmetic crosses the pragma below
 
 #pragma clang fp contract(off)
 
@@ -68,16 +69,8 @@ __global__ __launch_bounds__(VAD_THREADS) void frame_power_kernel(Vad a) {
     const float* row = a.wav + b * a.S;
     const int span_n = (live - 1) * a.hop + a.frame;
     auto one = [&](int i) {
-      int p = p0 + i;
-      float v;
-      if (a.pad_zero) {
-        v = p >= 0 && p < len ? row[p] : 0.f;
-      } else {  // the index rule of fs2_melspec
-        p = p < 0 ? -p : p;
-        p = p > len - 1 ? 2 * (len - 1) - p : p;
-        p = p < 0 ? 0 : p > len - 1 ? len - 1 : p;
-        v = row[p];
-      }
+      const int p = p0 + i;
+      const float v = a.pad_zero ? (p >= 0 && p < len ? row[p] : 0.f) : row[reflect_index(p, len)];
       sq[i] = v * v;
     };
     const int quads = a.wav_al16 && span_n > head ? (span_n - head) / 4 : 0;

@@ -786,9 +786,7 @@ def melspec(wav, lens, hop, window, twiddle, fb, n_mels, clip=False, energy=True
         raise RuntimeError("melspec: wav is f32 (B, S)")
     if lens is not None and (lens.dtype != torch.int64 or lens.numel() != wav.shape[0]):
         raise RuntimeError("melspec: lens is int64 (B)")
-    if window.dtype != torch.float32 or window.numel() != 1024 or \
-            twiddle.dtype != torch.float32 or twiddle.numel() != 2048:
-        raise RuntimeError("melspec: window f32 (1024), twiddle f32 (1024, 2)")
+    _tables_f32("melspec", window, twiddle)
     if (first.dtype, count.dtype, off.dtype, w.dtype) != (torch.int32,) * 3 + (torch.float32,) or \
             not first.numel() == count.numel() == off.numel() == int(n_mels):
         raise RuntimeError("melspec: filterbank is (first, count, offset) int32 (n_mels) + f32 weights")
