@@ -157,7 +157,8 @@ int fs2_resblock1_fused(const void* x, int64_t rows, int64_t seq_len, int64_t ch
  *   wav[r] = tanh(bias + sum_{j<7, c} w[0, c, j] * x[r + j - 3, c])   (zero outside the
  *   utterance), x (rows, c_in) in the compute dtype; wav fp32 and, when pcm is not NULL,
  *   pcm[r] = (int16) (wav[r] * max_wav_value) truncated toward zero as numpy's astype.
- *   lens (optional, device, samples per utterance): rows t >= lens[b] are written as 0.     */
+ *   lens (optional, device, samples per utterance): rows t >= lens[b] are written as 0.
+ *   1 <= c_in <= 64: a 256-row block stages (256 + 6 + 7) * c_in fp32 in LDS, 68,864 B at 64. */
 int fs2_vocoder_post(int dtype, const void* x, int64_t rows, int64_t seq_len, int64_t c_in,
                      const int64_t* lens, const float* w, const float* bias, float max_wav_value,
                      float* wav, int16_t* pcm, void* stream);
