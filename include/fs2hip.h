@@ -772,6 +772,84 @@ int fs2_bn_bwd(int dtype, const float* dout, const float* z, const float* mean, 
                float* dgamma,
                float* dbeta, float* ws, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- ResCNN speaker encoder
+ * The 'rescnn' architecture of speech_embedder_net.py:19-63 (ConvNorm2D / ResBlock,
+ * module.py:59-117), fp32.  Activations are channels-last with time as the OUTER spatial axis:
+ * (n, w, h, c), w = time, h = mel -- the encoder's input (N, T, 80) is that layout with c = 1.
+ * A torch weight (c_out, c_in, kh, kw) has kh over h and kw over w.  Square odd kernels
+ * k <= 7, stride 1 or 2; output extents (w + 2 pad - k) / stride + 1.  c_out a multiple of 16;
+ * c_in = 1 (direct VALU kernels) or a multiple of 16 (implicit GEMM on the f32 MFMA).
+ *
+ * fs2_conv2d_weight_prep: the kernel layouts of w -- w_fwd for fs2_conv2d_fwd, w_bwd for
+ * fs2_conv2d_dgrad (either nullable), c_out * c_in * k * k floats each.
+ * fs2_conv2d_fwd: y = act(conv(x) + bias) with, in this order, bias (nullable), the folded
+ * eval-mode BatchNorm y * scale[c] + shift[c] (both or neither), + res (n, wo, ho, c_out)
+ * (nullable), ReLU (relu != 0).  One launch.
+ * fs2_conv2d_dgrad: dx (n, w, h, c_in) = the gradient of the input for dy (n, wo, ho, c_out),
+ * + add (same shape as dx, nullable): for stride 2 a gather over the output positions of
+ * matching parity.
+ * fs2_conv2d_wgrad: dw (c_out, c_in, k, k) in torch's layout and db (c_out, nullable); the
+ * output positions are split into slices whose partial results land in ws and are added in
+ * slice order.  beta = 0 overwrites, beta = 1 adds.                                       */
+int fs2_conv2d_weight_prep(const float* w, int64_t c_out, int64_t c_in, int k, float* w_fwd,
+                           float* w_bwd, void* stream);
+int fs2_conv2d_fwd(const float* x, int64_t n, int64_t w, int64_t h, int64_t c_in,
+                   const float* w_fwd, const float* bias, int64_t c_out, int k, int stride, int pad,
+                   const float* scale, const float* shift, const float* res, int relu, float* y,
+                   void* stream);
+int fs2_conv2d_dgrad(const float* dy, int64_t n, int64_t w, int64_t h, int64_t c_in,
+                     const float* w_bwd, int64_t c_out, int k, int stride, int pad,
+                     const float* add, float* dx, void* stream);
+int64_t fs2_conv2d_wgrad_ws_bytes(int64_t n, int64_t w, int64_t h, int64_t c_in, int64_t c_out,
+                                  int k, int stride, int pad);
+int fs2_conv2d_wgrad(const float* x, const float* dy, int64_t n, int64_t w, int64_t h,
+                     int64_t c_in, int64_t c_out, int k, int stride, int pad, float* dw, float* db,
+                     int beta, float* ws, int64_t ws_bytes, void* stream);
+/* Training-mode BatchNorm2d over (rows = n w h, c) + residual + ReLU (module.py:77-78,
+ * 111-117): out = relu(BN(z) + res) (res nullable, relu a flag).  Statistics as fs2_bn_fwd:
+ * per 256-row block the column sum and centred second moment, combined exactly in block
+ * order; biased variance normalises, the unbiased one goes into running_var with `momentum`;
+ * num_batches_tracked (nullable device int64) is incremented.  mean, rstd (c each) are kept
+ * for the backward.  c in 8, 16, 32, ... 1024.  ws: fs2_bn2d_ws_bytes(rows, c), either call.
+ * fs2_bn2d_bwd: g = dout * (out > 0) (rows, c) is written out -- it is also the gradient of
+ * res -- then dz; dgamma, dbeta (nullable) are overwritten.
+ * fs2_bn2d_fold: the eval-mode scale = gamma / sqrt(running_var + eps) and
+ * shift = beta - running_mean * scale that fs2_conv2d_fwd applies.                        */
+int64_t fs2_bn2d_ws_bytes(int64_t rows, int64_t c);
+int fs2_bn2d_fwd(const float* z, int64_t rows, int64_t c, const float* gamma, const float* beta,
+                 float eps, float momentum, float* running_mean, float* running_var,
+                 int64_t* num_batches_tracked, float* mean, float* rstd, const float* res, int relu,
+                 float* out, float* ws, int64_t ws_bytes, void* stream);
+int fs2_bn2d_fold(const float* gamma, const float* beta, const float* running_mean,
+                  const float* running_var, float eps, int64_t c, float* scale, float* shift,
+                  void* stream);
+int fs2_bn2d_bwd(const float* dout, const float* out, const float* z, const float* mean,
+                 const float* rstd, const float* gamma, int64_t rows, int64_t c, int relu, float* g,
+                 float* dz, float* dgamma, float* dbeta, float* ws, int64_t ws_bytes, void* stream);
+/* AdaptiveAvgPool2d((None, 1)) + Dropout + view(N, -1) (speech_embedder_net.py:60-62):
+ *   out[n, c * h_ext + h] = mean_w x[n, w, h, c] * keep,  keep = 0 or 1 / (1 - p)
+ * drawn for element n * c_ext * h_ext + c * h_ext + h of `site`; the backward regenerates it. */
+int fs2_pool_drop_fwd(const float* x, int64_t n, int64_t w, int64_t h, int64_t c, float p,
+                      const uint64_t* seed, uint64_t site, float* out, void* stream);
+int fs2_pool_drop_bwd(const float* dout, int64_t n, int64_t w, int64_t h, int64_t c, float p,
+                      const uint64_t* seed, uint64_t site, float* dx, void* stream);
+/* fs2_clf_head / fs2_clf_head_wgrad with the projection's input width d as an argument
+ * (a multiple of 64, <= 1024; 640 for the ResCNN): wp (64, d), wpt (d, 64), dwp (64, d).   */
+int fs2_clf_head_w(const float* x, int64_t ldx, int64_t n, int64_t d, const float* wp,
+                   const float* wpt, const float* bp, const float* w0, const float* w0t,
+                   const float* b0, const float* w1, const float* w1t, const float* b1,
+                   const float* w2, const float* b2, float p_drop, const uint64_t* seed,
+                   uint64_t site, float* emb, float* logit, const float* demb, const float* dlogit,
+                   float* dx, int64_t lddx, void* stream);
+int64_t fs2_clf_head_w_wgrad_ws_bytes(int64_t n);
+int fs2_clf_head_w_wgrad(const float* x, int64_t ldx, int64_t n, int64_t d, const float* wp,
+                         const float* wpt, const float* bp, const float* w0, const float* w0t,
+                         const float* b0, const float* w1, const float* w1t, const float* b1,
+                         const float* w2, const float* b2, float p_drop, const uint64_t* seed,
+                         uint64_t site, const float* demb, const float* dlogit, float* dwp,
+                         float* dbp, float* dw0, float* db0, float* dw1, float* db1, float* dw2,
+                         float* db2, int beta, float* ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- embeddings, adaptor
  * Encoder input: word_emb[text] + accent_emb[accent] + posenc[t] (transformer/Models.py:101-103). */
 int fs2_encoder_embed_fwd(const int64_t* texts, const int64_t* accents, const float* word_emb,

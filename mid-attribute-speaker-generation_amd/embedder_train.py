@@ -5,7 +5,7 @@
 ``EmbedderTrainer`` holds a ``SpeechEmbedder(weight_grads=True)``, a ``GE2ELoss`` and the
 reference's three ``torch.optim.Adam`` optimisers as ``fs2_adam_l2_step`` over one arena each:
 
-  main   LSTM stack + projection   lr 1e-3, weight_decay 1e-6, clipped at 3.0
+  main   encoder + projection      lr 1e-3, weight_decay 1e-6, clipped at 3.0
   ge2e   GE2ELoss.w, .b            lr 1e-3,                    clipped at 1.0
   da     the domain classifier     lr 1e-3, weight_decay 1e-6, clipped at 3.0
 
@@ -30,9 +30,12 @@ waveform through the mel front end (``audio.py``), ``spkr2embedding`` lines 289-
 Not ported: the per-batch random shuffle / unshuffle of lines 160-172 is drawn by the batcher
 (to keep Python's generator in step with the reference) but not applied -- the embedder treats
 the rows independently, so it only changes the order in which the gradient sums run; the
-silence split of ``process_dvector_wav`` (``librosa.effects.split``), the ``rescnn``
-architecture, the ``contrast`` loss, the t-SNE plots, DDP of the embedder, and the joint
-``train_ganlike.py`` loop.
+silence split of ``process_dvector_wav`` (``librosa.effects.split``), the ``contrast`` loss,
+the t-SNE plots, DDP of the embedder, and the joint ``train_ganlike.py`` loop.
+
+Either architecture of the encoder trains here: pass
+``SpeechEmbedder(device, True, architecture='rescnn')`` as ``embedder`` for the residual CNN;
+the "main" arena then holds its 48 convolution and BatchNorm parameters and the projection.
 """
 import contextlib
 import math
@@ -41,7 +44,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .ge2e import GE2ELoss, SpeechEmbedder, _BCESumFn
+from .ge2e import NMELS, GE2ELoss, SpeechEmbedder, _BCESumFn
 from .model import ParamArena
 
 ANNEAL_EPOCHS = (800, 1400, 1800, 2200)  # config/config.yaml train.anneal_epochs
@@ -218,8 +221,7 @@ class EmbedderTrainer:
         with self._eval():
             for _ in range(epochs):
                 if hasattr(batches, "next_batch"):
-                    it = (batches.next_batch()[0].view(batches.n_spk, batches.n_utt, -1,
-                                                       self.embedder.LSTM_stack.input_size)
+                    it = (batches.next_batch()[0].view(batches.n_spk, batches.n_utt, -1, NMELS)
                           for _ in range(batches.batches_per_epoch))
                 else:
                     it = iter(batches)

@@ -16,6 +16,10 @@ Mirrors ``Multilingual-Speaker-Encoder-with-Domain-Adaptation/speech_embedder_ne
   returned as NaN here as well.  For M > 1, the speaker-encoder training loss, the softmax
   GE2E loss is one kernel forward and one backward (``fs2_ge2e_softmax``); the 'contrast'
   variant is not built and raises.
+* ``SpeechEmbedder(architecture='rescnn')`` -- the reference's other feature extractor
+  (``hp.model.architecture``, ``speech_embedder_net.py:19-63,79-81``): a 2-D residual CNN over
+  the (mel, time) plane, 640 features, the same head behind a 640-wide projection
+  (``rescnn.py``, ``csrc/rescnn.hip``).  Same interface, the reference's state-dict keys.
 
 Kernels (``csrc/lstm.hip``): the 3-layer stack runs as a wavefront -- launch s computes
 layer l at step s - l, all layers in one launch (T + 2 launches instead of 3T), with the
@@ -120,19 +124,33 @@ def _linear_norm(in_dim, out_dim, dev):
 
 
 class SpeechEmbedder(nn.Module):
-    """``speech_embedder_net.py:65-146`` (LSTM architecture, language DA head).
+    """``speech_embedder_net.py:65-146`` (language DA head); ``architecture`` is
+    ``hp.model.architecture``: ``'LSTM'`` (``LSTM_stack``) or ``'rescnn'`` (``_feat_extractor``,
+    ``hp.model.hidden`` = 640).
 
     ``weight_grads=False`` is the ``--use_clf`` discriminator: the backward gives the input
     gradient only and no parameter gets a ``.grad``.  With ``True`` the backward also
     accumulates every parameter's gradient into ``.grad`` (``embedder_train.EmbedderTrainer``),
     and ``forward(x, detach=True)`` back-propagates into the classifier alone."""
 
-    def __init__(self, device="cuda", weight_grads=False):
+    def __init__(self, device="cuda", weight_grads=False, architecture="LSTM"):
         super().__init__()
+        if architecture not in ("LSTM", "rescnn"):
+            raise ValueError(f"architecture {architecture!r}: 'LSTM' or 'rescnn'")
+        self.architecture = architecture
         self.weight_grads = bool(weight_grads)
         dev = torch.device(device)
-        self.LSTM_stack = nn.LSTM(NMELS, HIDDEN, num_layers=LAYERS, batch_first=True, device=dev)
-        self.projection = _linear_norm(HIDDEN, PROJ, dev)
+        if architecture == "LSTM":
+            self.LSTM_stack = nn.LSTM(NMELS, HIDDEN, num_layers=LAYERS, batch_first=True,
+                                      device=dev)
+            self.hidden = HIDDEN
+        else:
+            from . import rescnn
+            self._feat_extractor = rescnn.ResCNN(dev)
+            self.hidden = rescnn.FEATURES
+            self.feat_dropout = rescnn.FEAT_DROPOUT
+            self.site_feat = 0x5E2F  # dropout stream of the pooled features
+        self.projection = _linear_norm(self.hidden, PROJ, dev)
         self.da_classifier = _Module()
         self.da_classifier.classifier = _Module()
         self.da_classifier.classifier.layer = nn.Sequential()
@@ -145,7 +163,8 @@ class SpeechEmbedder(nn.Module):
         self.seed(0x6E2E)
 
     def seed(self, s):
-        """Classifier dropout stream: call k draws key splitmix64(s, k) on the device."""
+        """Dropout streams (the classifier's and, for 'rescnn', the pooled features'; one key,
+        two sites): call k draws key splitmix64(s, k) on the device."""
         self._seed_base = int(s) & (2 ** 63 - 1)
         self._seed_state = None
 
@@ -155,7 +174,7 @@ class SpeechEmbedder(nn.Module):
         key = tuple(p._version for p in self.parameters())
         if self._key == key:
             return self._cache
-        dev = self.LSTM_stack.weight_ih_l0.device
+        dev = self.projection.linear_layer.weight.device
 
         def t(w):  # (out, in) -> (in, out)
             o, i = w.shape
@@ -163,6 +182,12 @@ class SpeechEmbedder(nn.Module):
             K.weight_prep(w.detach().contiguous(), o, i, 1, w_bwd=wt)
             return wt
 
+        if self.architecture == "rescnn":
+            from . import rescnn
+            self._cache = {"conv": rescnn.prep(self._feat_extractor)}
+            self._cache.update(self._prep_head(t))
+            self._key = key
+            return self._cache
         lstm = []
         for l in range(LAYERS):
             w_ih = getattr(self.LSTM_stack, f"weight_ih_l{l}").detach().contiguous()
@@ -179,33 +204,42 @@ class SpeechEmbedder(nn.Module):
             "w_hh_t": torch.stack([lstm[l]["w_hh_t"] for l in range(LAYERS)]),
             "bias": torch.stack([lstm[l]["bias"] for l in range(LAYERS)]),
         }
-        L = [self.projection.linear_layer] + [
-            getattr(self.da_classifier.classifier.layer, f"linear_{i}").linear_layer
-            for i in range(3)]
+        self._cache = {"lstm": lstm, "stack": stack}
+        self._cache.update(self._prep_head(t))
+        self._key = key
+        return self._cache
+
+    def _prep_head(self, t):
+        L = self._head_layers()
         wts = [l.weight.detach().contiguous() for l in L]
         bs = [l.bias.detach().contiguous() for l in L]
         keep = (wts[0], t(wts[0]), bs[0], wts[1], t(wts[1]), bs[1], wts[2], t(wts[2]), bs[2],
                 wts[3], bs[3])
-        head = tuple(_p(a) for a in keep)
-        self._cache = {"lstm": lstm, "stack": stack, "head": head, "keep": keep}
-        self._key = key
-        return self._cache
+        return {"head": tuple(_p(a) for a in keep), "keep": keep}
 
     def forward(self, x, detach=False):
         """x (N, 150, 80) fp32 on the GPU -> {'embeddings': (N, 64), 'da_lang_logits': (N,)}."""
+        fn = _EmbedderFn
+        drops = self.da_dropout
+        if self.architecture == "rescnn":
+            from .rescnn import _ResCNNEmbedderFn as fn
+            if x.dim() != 3 or x.shape[2] != NMELS:
+                raise ValueError(f"rescnn embedder: input {tuple(x.shape)}, expected (N, T, "
+                                 f"{NMELS})")
+            drops = max(self.da_dropout, self.feat_dropout)
         if self._seed_state is None:
             self._seed_state = torch.tensor([self._seed_base, 0, 0], dtype=torch.int64,
                                             device=x.device)
-        if self.training and self.da_dropout > 0:
-            K.seed_next(self._seed_state)  # a fresh classifier dropout key per call
+        if self.training and drops > 0:
+            K.seed_next(self._seed_state)  # a fresh dropout key per call
         seed = self._seed_state[2:3].clone()  # this call's key (the backward re-reads it)
         if self.weight_grads:
             # the parameters are not inputs of the function (their gradients are accumulated
             # by hand); one of them rides along so that autograd runs the backward
-            emb, logit = _EmbedderFn.apply(x.float(), self, seed, bool(detach),
-                                           self.projection.linear_layer.bias)
+            emb, logit = fn.apply(x.float(), self, seed, bool(detach),
+                                  self.projection.linear_layer.bias)
         else:
-            emb, logit = _EmbedderFn.apply(x.float(), self, seed, False, None)
+            emb, logit = fn.apply(x.float(), self, seed, False, None)
         if detach:
             emb = emb.detach()
         return {"embeddings": emb, "da_lang_logits": logit}
@@ -220,7 +254,8 @@ class SpeechEmbedder(nn.Module):
         return list(self.da_classifier.parameters())
 
     def main_parameters(self):
-        return list(self.LSTM_stack.parameters()) + list(self.projection.parameters())
+        feat = self.LSTM_stack if self.architecture == "LSTM" else self._feat_extractor
+        return list(feat.parameters()) + list(self.projection.parameters())
 
     def compute_embedding(self, x):
         """``{'embeddings': (N, 64)}`` without the classifier's output."""
@@ -236,17 +271,22 @@ class SpeechEmbedder(nn.Module):
 
     def _head_wgrad(self, last, ldx, n, w, p, seed, demb, dlogit, detach):
         dev = seed.device
-        sizes = [PROJ * HIDDEN, PROJ, PROJ * PROJ, PROJ, PROJ * PROJ, PROJ, PROJ, 1]
+        sizes = [PROJ * self.hidden, PROJ, PROJ * PROJ, PROJ, PROJ * PROJ, PROJ, PROJ, 1]
         buf = torch.empty(sum((s + 3) // 4 * 4 for s in sizes), device=dev)
         outs, o = [], 0
         for s in sizes:
             outs.append(buf[o:o + s])
             o += (s + 3) // 4 * 4
-        nb = lib.fs2_clf_head_wgrad_ws_bytes(n)
-        ws = K.ws(nb, dev)
-        lib.fs2_clf_head_wgrad(last, ldx, n, *w["head"], p, _p(seed) if p > 0 else None, self.site,
-                               K.ptr(demb), K.ptr(dlogit), *[_p(t) for t in outs], 0, _p(ws), nb,
-                               K.stream())
+        tail = (*w["head"], p, _p(seed) if p > 0 else None, self.site, K.ptr(demb), K.ptr(dlogit),
+                *[_p(t) for t in outs], 0)
+        if self.architecture == "LSTM":
+            nb = lib.fs2_clf_head_wgrad_ws_bytes(n)
+            ws = K.ws(nb, dev)
+            lib.fs2_clf_head_wgrad(last, ldx, n, *tail, _p(ws), nb, K.stream())
+        else:
+            nb = lib.fs2_clf_head_w_wgrad_ws_bytes(n)
+            ws = K.ws(nb, dev)
+            lib.fs2_clf_head_w_wgrad(last, ldx, n, self.hidden, *tail, _p(ws), nb, K.stream())
         for i, lin in enumerate(self._head_layers()):
             if i == 0 and detach:  # the classifier saw a detached embedding
                 continue
