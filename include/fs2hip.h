@@ -285,6 +285,78 @@ int fs2_ge2e_eer(const float* enroll, const float* verify, int64_t n_spk, int64_
  * logit are each nullable (their total then stays); correct (nullable) receives the count.   */
 int fs2_epoch_stats_add(float* totals, const float* loss, const float* da_loss, const float* logit,
                         const float* y, int64_t n, float* correct, void* stream);
+/* ---- Exact t-SNE of speaker embeddings (train_speech_embedder.py:311-385; the semantics of
+ * scikit-learn's TSNE(2, init='pca', method='exact'), Euclidean metric).  fp32 storage; limits
+ * for every entry: n <= 4096 points, dim <= 1024, 2 output components.  n = 0 launches nothing.
+ * Every accumulation runs in a fixed order (no atomics): results are bitwise repeatable.
+ *
+ * fs2_tsne_points: out[s] (n, dim) = the plain mean of the first min(count_s, cap) rows of
+ * segment s of x (rows, dim), rows seg_start[s] .. seg_start[s + 1] - 1 (device int64[n + 1],
+ * non-decreasing), added in row order; no renormalisation (embs[indices, :cap].mean(1)).  An
+ * empty segment gives NaN.  cap >= 1.                                                       */
+int fs2_tsne_points(const float* x, const int64_t* seg_start, int64_t n, int64_t dim, int64_t cap,
+                    float* out, void* stream);
+/* Y0 (n, 2) = the PCA initialisation: X centred, the dim x dim covariance and its two leading
+ * eigenvectors in fp64 (subspace iteration with a Rayleigh-Ritz rotation, at most 1000 rounds,
+ * so it ends on a degenerate spectrum too), each component's sign such that its
+ * largest-magnitude loading is positive (svd_flip, V-based), Y0 = Xc V scaled by
+ * 1e-4 / std(Y0[:, 0]) (population std).  ws: fs2_tsne_pca_ws_bytes.                          */
+int64_t fs2_tsne_pca_ws_bytes(int64_t n, int64_t dim);
+int fs2_tsne_pca_init(const float* X, int64_t n, int64_t dim, float* Y0, void* ws,
+                      int64_t ws_bytes, void* stream);
+/* P (n, n) fp32 = the joint probabilities of _joint_probabilities: squared distances from the
+ * direct (x_i - x_j)^2 form (fp64 sums rounded to fp32); per row the binary search of
+ * _binary_search_perplexity in fp64 (beta from 1, at most 100 steps, |H - log(perplexity)| <=
+ * float(1e-5), doubling / halving while the far bound is infinite, a zero row sum becomes
+ * float(1e-8), the diagonal excluded); P = max((C + C^T) / max(sum, eps), eps) with eps the
+ * fp64 machine epsilon, zero diagonal.  0 < perplexity < n.  beta (fp64[n]) and P64 (fp64
+ * (n, n), P before its rounding) are optional.  ws: fs2_tsne_affinities_ws_bytes.            */
+int64_t fs2_tsne_affinities_ws_bytes(int64_t n);
+int fs2_tsne_affinities(const float* X, int64_t n, int64_t dim, double perplexity, float* P,
+                        double* beta, double* P64, void* ws, int64_t ws_bytes, void* stream);
+/* The descent's device record, double[16]: {iteration, stage (1, 2), best error, best
+ * iteration, done, n_iter, last evaluated error, first iteration of the stage, gradient norm at
+ * the last check, max_iter, exploration_iter, n_iter_without_progress, early_exaggeration,
+ * learning_rate, min_grad_norm, 0}.  exploration_iter, max_iter >= 1, 0 < perplexity < n.    */
+int fs2_tsne_state_init(double* state, int64_t n, double perplexity, int64_t max_iter,
+                        int64_t exploration_iter, int64_t n_iter_without_progress,
+                        double early_exaggeration, double learning_rate, double min_grad_norm,
+                        void* stream);
+/* Phase A of iteration: rowsum[i] (fp64[n]) = sum_{j != i} w_ij, w = 1 / (1 + |y_i - y_j|^2)
+ * in fp32, summed in fp64.  state (nullable): returns at once when the record says done.    */
+int fs2_tsne_rowsum(const float* Y, int64_t n, const double* state, double* rowsum, void* stream);
+/* Phase B of iteration `iter`: Z = sum of rowsum (every block in the same order), q = max(w / Z,
+ * eps), grad_i = 4 sum_j (e p_ij - q_ij) w_ij (y_i - y_j); gains += 0.2 where update * grad < 0,
+ * else *= 0.8, floor 0.01; grad *= gains; update = momentum update - lr grad; Y_out = Y + update
+ * (Y_out != Y: other rows still read Y).  Exaggeration e, momentum (0.5 / 0.8) and lr come from
+ * the record's stage; at the first iteration of stage 2 update is read as 0 and gains as 1.
+ * gn_rows[i] = the row's share of |gains grad|^2.  On an evaluating iteration ((iter + 1) % 50
+ * == 0 or the last iteration of the stage) kl_rows[i] = sum_j e p_ij log(max(e p_ij, eps) /
+ * q_ij) of Y (fp64 from the fp32 pair terms; this phase knows Z, so phase A leaves the error
+ * to it).  Returns at once when the record says done.                                       */
+int fs2_tsne_update(const float* P, const float* Y, float* Y_out, float* update, float* gains,
+                    int64_t n, int64_t iter, const double* state, const double* rowsum,
+                    double* kl_rows, double* gn_rows, void* stream);
+/* One launch per check iteration, per last iteration of a stage: the rules of
+ * _gradient_descent on the record with error = sum kl_rows, grad_norm = sqrt(sum gn_rows).  At
+ * (iter + 1) % 50 == 0: error < best records a new best, otherwise iter - best_iter > window
+ * ends the stage (window: exploration_iter in stage 1, n_iter_without_progress in stage 2);
+ * then grad_norm <= min_grad_norm ends it.  The last iteration of a stage (exploration_iter - 1,
+ * max_iter - 1) ends it too.  After stage 1, stage 2 starts at iter + 1 with best reset (stage 1
+ * runs to exploration_iter whatever max_iter is, as sklearn's; if it ends at or past
+ * max_iter - 1 there is no stage 2); after the last stage, done = 1 and n_iter = iter.      */
+int fs2_tsne_control(double* state, int64_t n, int64_t iter, const double* kl_rows,
+                     const double* gn_rows, void* stream);
+/* Phases A and B once on explicit scalars, no record (tests, single steps): always evaluates
+ * kl_rows.  fs2_tsne_kl: kl[0] = the error of Y under exaggeration * P, nothing updated.     */
+int fs2_tsne_step(const float* P, const float* Y, float* Y_out, float* update, float* gains,
+                  int64_t n, double exaggeration, double momentum, double learning_rate,
+                  double* rowsum, double* kl_rows, double* gn_rows, void* stream);
+int fs2_tsne_kl(const float* P, const float* Y, int64_t n, double exaggeration, double* rowsum,
+                double* kl_rows, double* kl, void* stream);
+/* out (n, 2) = (Y - min) / (max - min) per column (visualize_embeddings:366); a constant
+ * column gives NaN, as numpy does.                                                          */
+int fs2_tsne_finish(const float* Y, int64_t n, float* out, void* stream);
 /* The mel front end (preprocessor/preprocessor.py:330-336; common/layers.py:101-123 over
  * common/stft.py) of a ragged batch in one launch: wav (batch, samples) fp32, lens (device
  * int64, nullable = samples for every row; read clamped into [1, samples]).  Per row, frames

@@ -25,13 +25,14 @@ Around the step (``embedder_data.SpeakerBatcher`` supplies the batches, cut on t
 kept on the device and read once per epoch, ``da_subroutine`` lines 249-287 (one read per pass),
 ``evaluate_eer`` the EER ``test()`` of 401-455 scored by ``fs2_ge2e_eer``, ``dvector`` the
 d-vector of 49-54 and 75-78 from a mel spectrogram, ``dvector_from_wav`` the same from a
-waveform through the mel front end (``audio.py``), ``spkr2embedding`` lines 289-309.
+waveform through the mel front end (``audio.py``), ``spkr2embedding`` lines 289-309,
+``visualize_embeddings`` the t-SNE map of 311-385 (``embedding_map.py``).
 
 Not ported: the per-batch random shuffle / unshuffle of lines 160-172 is drawn by the batcher
 (to keep Python's generator in step with the reference) but not applied -- the embedder treats
 the rows independently, so it only changes the order in which the gradient sums run; the
 silence split of ``process_dvector_wav`` (``librosa.effects.split``), the ``contrast`` loss,
-the t-SNE plots, DDP of the embedder, and the joint ``train_ganlike.py`` loop.
+DDP of the embedder, and the joint ``train_ganlike.py`` loop.
 
 Either architecture of the encoder trains here: pass
 ``SpeechEmbedder(device, True, architecture='rescnn')`` as ``embedder`` for the residual CNN;
@@ -358,6 +359,19 @@ class EmbedderTrainer:
                 mels, _ = batcher.speaker_batch(k, utter_num)
                 out[name] = self.embedder.compute_embedding(mels)["embeddings"]
         return out
+
+    def visualize_embeddings(self, source, path=None, **kw):
+        """visualize_embeddings (311-385): the t-SNE map of the speakers' mean embeddings,
+        coloured by language.  ``source`` is a batcher (``spkr2embedding`` runs on it) or a ready
+        ``{file name: embeddings}`` dict; ``kw`` goes to ``embedding_map.speaker_map``.  Returns
+        the map and, given ``path``, writes the figure there."""
+        from . import embedding_map
+        if not isinstance(source, dict):
+            source = self.spkr2embedding(source)
+        m = embedding_map.speaker_map(source, **kw)
+        if path is not None:
+            embedding_map.plot_speaker_map(m, path)
+        return m
 
     def anneal(self, epoch):
         """lr_schedule (83-95): halve the lr of ``main`` and ``ge2e`` at the anneal epochs."""

@@ -772,6 +772,152 @@ def rows_mean_unit(x, seg_start):
     return out
 
 
+# ------------------------------------------------------------------ exact t-SNE
+def empty_f64(shape, device):
+    return torch.empty(shape, dtype=torch.float64, device=device)
+
+
+def _tsne_y(name, *ts):
+    _dev(*ts)
+    for t in ts:
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 2 or t.shape != ts[0].shape:
+            raise RuntimeError(f"{name}: embeddings, updates and gains are f32 (n, 2)")
+    return ts[0].shape[0]
+
+
+def _tsne_p(name, P, n, *f64s):
+    _dev(P, *f64s)
+    if P.dtype != torch.float32 or tuple(P.shape) != (n, n):
+        raise RuntimeError(f"{name}: P is f32 ({n}, {n})")
+    for t in f64s:
+        if t.dtype != torch.float64 or t.numel() < n:
+            raise RuntimeError(f"{name}: the row buffers are f64 with at least {n} elements")
+
+
+def _tsne_state(name, state):
+    _dev(state)
+    if state.dtype != torch.float64 or state.numel() != 16:
+        raise RuntimeError(f"{name}: state is f64[16] (tsne_state)")
+
+
+def tsne_points(x, seg_start, cap):
+    """x (rows, dim), seg_start device int64 (n + 1) -> (n, dim): the plain mean of each
+    segment's first ``cap`` rows (fs2_tsne_points)."""
+    _dev(x, seg_start)
+    if x.dtype != torch.float32 or seg_start.dtype != torch.int64 or x.dim() != 2:
+        raise RuntimeError("tsne_points: x f32 (rows, dim), seg_start i64")
+    n = seg_start.numel() - 1
+    out = torch.empty((n, x.shape[1]), dtype=torch.float32, device=x.device)
+    lib.fs2_tsne_points(ptr(x), ptr(seg_start), n, x.shape[1], int(cap), ptr(out), stream())
+    return out
+
+
+def _tsne_x(name, X):
+    _dev(X)
+    if X.dtype != torch.float32 or X.dim() != 2:
+        raise RuntimeError(f"{name}: X is f32 (n, dim)")
+    return X.shape
+
+
+def tsne_pca_init(X):
+    """X (n, dim) -> Y0 (n, 2): the two leading principal components, the first scaled to
+    standard deviation 1e-4 (fs2_tsne_pca_init)."""
+    n, dim = _tsne_x("tsne_pca_init", X)
+    Y0 = torch.empty((n, 2), dtype=torch.float32, device=X.device)
+    nb = lib.fs2_tsne_pca_ws_bytes(n, dim)
+    wk = empty_f64(max(nb // 8, 1), X.device)
+    lib.fs2_tsne_pca_init(ptr(X), n, dim, ptr(Y0), ptr(wk), nb, stream())
+    return Y0
+
+
+def tsne_affinities(X, perplexity, want64=False):
+    """X (n, dim) -> the joint probabilities P (n, n) f32 of exact t-SNE; with ``want64`` also
+    beta (n) and P before its rounding, both f64 (fs2_tsne_affinities)."""
+    n, dim = _tsne_x("tsne_affinities", X)
+    dev = X.device
+    P = torch.empty((n, n), dtype=torch.float32, device=dev)
+    beta = empty_f64(n, dev) if want64 else None
+    P64 = empty_f64((n, n), dev) if want64 else None
+    nb = lib.fs2_tsne_affinities_ws_bytes(n)
+    wk = empty_f64(max(nb // 8, 1), dev)
+    lib.fs2_tsne_affinities(ptr(X), n, dim, float(perplexity), ptr(P), ptr(beta), ptr(P64),
+                            ptr(wk), nb, stream())
+    return (P, beta, P64) if want64 else P
+
+
+def tsne_state(n, perplexity, max_iter, exploration_iter, n_iter_without_progress,
+               early_exaggeration, learning_rate, min_grad_norm, device):
+    """The descent's device record, f64[16] (fs2_tsne_state_init)."""
+    state = empty_f64(16, device)
+    lib.fs2_tsne_state_init(ptr(state), int(n), float(perplexity), int(max_iter),
+                            int(exploration_iter), int(n_iter_without_progress),
+                            float(early_exaggeration), float(learning_rate), float(min_grad_norm),
+                            stream())
+    return state
+
+
+def tsne_rowsum(Y, state, rowsum):
+    """Phase A of an iteration: rowsum (n) f64 = the rows' sums of w (fs2_tsne_rowsum)."""
+    n = _tsne_y("tsne_rowsum", Y)
+    _tsne_state("tsne_rowsum", state)
+    if rowsum.dtype != torch.float64 or rowsum.numel() < n or not rowsum.is_cuda:
+        raise RuntimeError(f"tsne_rowsum: rowsum is f64 with at least {n} elements")
+    lib.fs2_tsne_rowsum(ptr(Y), n, ptr(state), ptr(rowsum), stream())
+
+
+def tsne_update(P, Y, Y_out, update, gains, it, state, rowsum, kl_rows, gn_rows):
+    """Phase B of iteration ``it``: gradient, gains, update and Y_out = Y + update; stage,
+    exaggeration and momentum come from ``state`` (fs2_tsne_update)."""
+    n = _tsne_y("tsne_update", Y, Y_out, update, gains)
+    _tsne_p("tsne_update", P, n, rowsum, kl_rows, gn_rows)
+    _tsne_state("tsne_update", state)
+    lib.fs2_tsne_update(ptr(P), ptr(Y), ptr(Y_out), ptr(update), ptr(gains), n, int(it),
+                        ptr(state), ptr(rowsum), ptr(kl_rows), ptr(gn_rows), stream())
+
+
+def tsne_control(state, n, it, kl_rows, gn_rows):
+    """The stopping and stage rules for iteration ``it`` on the record (fs2_tsne_control)."""
+    _tsne_state("tsne_control", state)
+    _dev(kl_rows, gn_rows)
+    if min(kl_rows.numel(), gn_rows.numel()) < n or kl_rows.dtype != torch.float64 or \
+            gn_rows.dtype != torch.float64:
+        raise RuntimeError(f"tsne_control: the row buffers are f64 with at least {n} elements")
+    lib.fs2_tsne_control(ptr(state), int(n), int(it), ptr(kl_rows), ptr(gn_rows), stream())
+
+
+def tsne_step(P, Y, update, gains, exaggeration, momentum, learning_rate):
+    """One iteration on explicit state: (Y', kl_rows (n) f64, gn_rows (n) f64); ``update`` and
+    ``gains`` are advanced in place (fs2_tsne_step)."""
+    n = _tsne_y("tsne_step", Y, update, gains)
+    _tsne_p("tsne_step", P, n)
+    dev = Y.device
+    Y_out = torch.empty_like(Y)
+    rowsum, kl_rows, gn_rows = empty_f64(n, dev), empty_f64(n, dev), empty_f64(n, dev)
+    lib.fs2_tsne_step(ptr(P), ptr(Y), ptr(Y_out), ptr(update), ptr(gains), n, float(exaggeration),
+                      float(momentum), float(learning_rate), ptr(rowsum), ptr(kl_rows),
+                      ptr(gn_rows), stream())
+    return Y_out, kl_rows, gn_rows
+
+
+def tsne_kl(P, Y, exaggeration=1.0):
+    """The objective of Y (n, 2) under ``exaggeration * P``: f64[1] on the device (fs2_tsne_kl)."""
+    n = _tsne_y("tsne_kl", Y)
+    _tsne_p("tsne_kl", P, n)
+    dev = Y.device
+    rowsum, kl_rows, kl = empty_f64(n, dev), empty_f64(n, dev), empty_f64(1, dev)
+    lib.fs2_tsne_kl(ptr(P), ptr(Y), n, float(exaggeration), ptr(rowsum), ptr(kl_rows), ptr(kl),
+                    stream())
+    return kl
+
+
+def tsne_finish(Y):
+    """(Y - min) / (max - min) per column (fs2_tsne_finish)."""
+    n = _tsne_y("tsne_finish", Y)
+    out = torch.empty_like(Y)
+    lib.fs2_tsne_finish(ptr(Y), n, ptr(out), stream())
+    return out
+
+
 def melspec(wav, lens, hop, window, twiddle, fb, n_mels, clip=False, energy=True, mag=False,
             log_mag=False, n_fft=1024, out=None):
     """The mel front end of a ragged batch (fs2_melspec): wav (B, S) f32, lens device int64 (B)
