@@ -560,12 +560,15 @@ int fs2_weight_prep_batch(int dtype, const int64_t* jobs, int n_jobs, int64_t n_
                           void* stream);
 
 /* Kernel-selection knobs for benchmarking (0 = automatic choice, the default).  Variants that
- * measured slower or neutral were removed in round 4 (their A/B records stay in profiles/):
+ * measured slower or neutral were removed in round 4 (their A/B records stay in profiles/).
+ * The conv / GEMM knobs are read in one place, the planner (csrc/conv_plan.hpp), which maps a
+ * shape and these knobs to a kernel; fs2_debug_conv_plan prints its answer.
  *   FS2_TUNE_GEMM_STAGES   fwd/dX LDS stages (1..4) of the tap-major kernel
  *   FS2_TUNE_WGRAD_STAGES  weight-gradient LDS stages (1..4) of the tap-major wgrad kernel
  *   FS2_TUNE_WGRAD_TILE    weight-gradient tile width (64 or 128) of the tap-major wgrad kernel
  *   FS2_TUNE_WGRAD_SPLITS  weight-gradient row splits (1..64) of the split-K wgrad kernels
- *   FS2_TUNE_LEGACY_GEMM   1 = the register-staged bf16 kernels of round 1 (A/B against round 1)
+ *   FS2_TUNE_RESERVED_4    (was FS2_TUNE_LEGACY_GEMM: the register-staged bf16 kernels of round
+ *                          1, removed; setting it to a non-zero value is FS2_ERR_ARG)
  *   FS2_TUNE_NT_GROUP      fwd/dX n-tiles per L2 tile group
  *   FS2_TUNE_NT_HALO       fwd/dX Conv1d (taps > 1) halo kernel: 0 = automatic (8-wave 256 x 128
  *                          tiles for the wide c_in <= 256 forward shapes, else 4-wave tiles by
@@ -609,13 +612,34 @@ int fs2_weight_prep_batch(int dtype, const int64_t* jobs, int n_jobs, int64_t n_
  *                          -1 = off (band / split-K halo kernels), n > 1 = everywhere, n splits
  * Process-wide; query workspace sizes after setting.                                 */
 enum { FS2_TUNE_GEMM_STAGES = 0, FS2_TUNE_WGRAD_STAGES = 1, FS2_TUNE_WGRAD_TILE = 2,
-       FS2_TUNE_WGRAD_SPLITS = 3, FS2_TUNE_LEGACY_GEMM = 4, FS2_TUNE_NT_GROUP = 5,
+       FS2_TUNE_WGRAD_SPLITS = 3, FS2_TUNE_RESERVED_4 = 4, FS2_TUNE_NT_GROUP = 5,
        FS2_TUNE_NT_HALO = 6, FS2_TUNE_WGRAD_HALO = 7, FS2_TUNE_HALO_SPLITK = 8,
        FS2_TUNE_ATTN = 9, FS2_TUNE_NT_TILE = 10, FS2_TUNE_LN_TILE = 11, FS2_TUNE_WGRAD_K1 = 12,
        FS2_TUNE_NT_K1 = 13, FS2_TUNE_ATTN_DMA = 14, FS2_TUNE_TAPREG = 15,
        FS2_TUNE_WGRAD_BAND = 16, FS2_TUNE_ATTN_XCD = 17, FS2_TUNE_WGRAD_K1M_STAGES = 18,
        FS2_TUNE_WGRAD_WIDE = 19, FS2_TUNE_COUNT = 20 };
 int fs2_set_tuning(int knob, int value);
+
+/* Which kernel a bf16 conv / GEMM call of this shape runs under the current knobs (debug; host
+ * only: nothing is launched and no GPU is needed).  op: FS2_PLAN_GEMM (fs2_conv_gemm / _ex),
+ * FS2_PLAN_GEMM_LN, FS2_PLAN_GEMM_LN_BWD, FS2_PLAN_WGRAD (fs2_conv_wgrad) or
+ * FS2_PLAN_WGRAD_K1_MULTI (jobs / n_jobs as in fs2_conv_wgrad_k1_multi: only db != 0, c_in and
+ * c_out of each row are read; NULL for the other ops).  facts: FS2_PLAN_* bits for what the
+ * dispatch reads off the pointers -- VEC (8-wide epilogue legal: c_out, ldy, ld_aux multiples
+ * of 8; y, bias, aux, y2 16-B aligned), HAS_Y, HAS_LENS, HAS_DB, DW16 (dw 16-B aligned), WS16
+ * (ws given and 16-B aligned).  cu_count: the device's compute units (256 on MI355X).
+ * Writes "<kernel> grid=G group=g kz=k reduce=<kernel or -> reduce_grid=R" to out (cap bytes):
+ * the kernel in the profiler's demangled form without "void fs2::" and the argument list,
+ * e.g. conv_gemm_tapreg<128, 64, 2, 2, 4, 9, 2, 3>; grid in workgroups (split factor
+ * included); kz = the split count (channel-block splits of the halo kernel, row splits of the
+ * weight gradients; 0 or 1 = none). */
+enum { FS2_PLAN_GEMM = 0, FS2_PLAN_GEMM_LN = 1, FS2_PLAN_GEMM_LN_BWD = 2, FS2_PLAN_WGRAD = 3,
+       FS2_PLAN_WGRAD_K1_MULTI = 4 };
+enum { FS2_PLAN_VEC = 1, FS2_PLAN_HAS_Y = 2, FS2_PLAN_HAS_LENS = 4, FS2_PLAN_HAS_DB = 8,
+       FS2_PLAN_DW16 = 16, FS2_PLAN_WS16 = 32 };
+int fs2_debug_conv_plan(int op, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out,
+                        int taps, int pad, int dilation, int flags, int facts,
+                        const int64_t* jobs, int n_jobs, int cu_count, char* out, int cap);
 
 /* ---------------------------------------------------------------- one FFT block per call
  * transformer/Layers.py:21-30 (FFTBlock.forward: MultiHeadAttention SubLayers.py:29-57, then

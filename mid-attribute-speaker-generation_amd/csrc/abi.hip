@@ -132,6 +132,9 @@ int fs2_abi_version(void) { return 1; }
 
 int fs2_set_tuning(int knob, int value) {
   FS2_CHECK_ARG(knob >= 0 && knob < FS2_TUNE_COUNT, "fs2_set_tuning: unknown knob %d", knob);
+  FS2_CHECK_ARG(knob != FS2_TUNE_RESERVED_4 || value == 0,
+                "fs2_set_tuning: knob 4 selected the register-staged bf16 kernels of round 1, "
+                "which are gone");
   g_tune[knob] = value;
   return FS2_OK;
 }

@@ -16,14 +16,9 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "glds.hpp"
 
 namespace fs2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 namespace {
 constexpr int DH = 128;
@@ -38,12 +33,6 @@ constexpr int LDR = DH + 16;
 constexpr int LDT = DH + 16;
 
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-FS2_DEV float bf2f(u16 v) { return __uint_as_float(((uint32_t)v) << 16); }
-FS2_DEV u16 f2bf(float f) {
-  __bf16 b = (__bf16)f;
-  return *reinterpret_cast<u16*>(&b);
-}
 
 // register-staged copy of a 64 x 128 tile by NT threads: 1024 16-B pieces, PER = 1024 / NT
 // per thread (issued before the MFMA work on the previous tile, so the global latency
@@ -137,8 +126,8 @@ FS2_DEV void accum_t2(f32x4 (&acc)[2][8], const u16* S, int rb, const bf16x8& w0
 
 FS2_DEV void store4_bf16(u16* p, const f32x4& v) {
   uint2 w;
-  w.x = (uint32_t)f2bf(v.x) | ((uint32_t)f2bf(v.y) << 16);
-  w.y = (uint32_t)f2bf(v.z) | ((uint32_t)f2bf(v.w) << 16);
+  w.x = (uint32_t)to_bf16(v.x) | ((uint32_t)to_bf16(v.y) << 16);
+  w.y = (uint32_t)to_bf16(v.z) | ((uint32_t)to_bf16(v.w) << 16);
   *reinterpret_cast<uint2*>(p) = w;
 }
 
@@ -149,10 +138,10 @@ FS2_DEV void store4_bf16(u16* p, const f32x4& v) {
 // Half the store instructions of an issue-bound store tail (the guide's T21, for 16-lane rows);
 // same bytes, same values.  p = the row's column 32d; both lanes of a pair must be active.
 FS2_DEV void store8x2_bf16(u16* p, const f32x4& a, const f32x4& b, int g) {
-  const uint32_t a0 = (uint32_t)f2bf(a.x) | ((uint32_t)f2bf(a.y) << 16);
-  const uint32_t a1 = (uint32_t)f2bf(a.z) | ((uint32_t)f2bf(a.w) << 16);
-  const uint32_t b0 = (uint32_t)f2bf(b.x) | ((uint32_t)f2bf(b.y) << 16);
-  const uint32_t b1 = (uint32_t)f2bf(b.z) | ((uint32_t)f2bf(b.w) << 16);
+  const uint32_t a0 = (uint32_t)to_bf16(a.x) | ((uint32_t)to_bf16(a.y) << 16);
+  const uint32_t a1 = (uint32_t)to_bf16(a.z) | ((uint32_t)to_bf16(a.w) << 16);
+  const uint32_t b0 = (uint32_t)to_bf16(b.x) | ((uint32_t)to_bf16(b.y) << 16);
+  const uint32_t b1 = (uint32_t)to_bf16(b.z) | ((uint32_t)to_bf16(b.w) << 16);
   const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
   const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
   const bool odd = g & 1;

@@ -12,7 +12,6 @@
 
 #define FS2_DEV __device__ __forceinline__
 
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -72,7 +71,7 @@ struct VocEpi {
   float alpha2 = 0.f;
 };
 
-// bf16 launchers (gemm_bf16.hip)
+// bf16 conv / GEMM dispatch (conv_dispatch.hip): plan (conv_plan.hpp), then launch
 int conv_gemm_bf16_launch(const void* x, int64_t ldx, const void* wk, void* y, int64_t ldy,
                           int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out, int taps,
                           int pad, const int64_t* lens, const float* bias, int flags,
@@ -88,30 +87,30 @@ int conv_gemm_lnbwd_glds_launch(const void* x, int64_t ldx, const void* wk, int6
                                 const float* rstd, const float* gamma, float p_in,
                                 const uint64_t* seed, uint64_t site_in, float* dres, int dres_add,
                                 void* dy_t, float* ws, hipStream_t st);
-int conv_gemm_glds_launch(const void* x, int64_t ldx, const void* wk, void* y, int64_t ldy,
-                          int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out, int taps,
-                          int pad, const int64_t* lens, const float* bias, int flags,
-                          const void* aux, int64_t ld_aux, const VocEpi& ve, hipStream_t st);
-int conv_wgrad_glds_launch(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw,
-                           float* db, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out,
-                           int taps, int pad, const int64_t* lens, int splits, int tile, float* ws,
-                           hipStream_t st);
-// returned by a launcher whose kernel does not apply to the shape (the caller tries the next
-// one); distinct from every FS2_ERR_* status, so an argument error is never taken for it
-constexpr int kNotEligible = 1;
-int conv_wgrad_band_launch(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw,
-                           float* db, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out,
-                           int taps, int pad, const int64_t* lens, hipStream_t st);
-int conv_wgrad_wide_launch(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw,
-                           float* db, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out,
-                           int taps, int pad, const int64_t* lens, float* ws, hipStream_t st);
-int64_t conv_wgrad_wide_ws_floats(int64_t rows, int64_t c_in, int64_t c_out, int taps);
-int64_t wgrad_k1_multi_ws_floats(const int64_t* jobs, int n, int64_t rows);
-int wgrad_k1_multi_launch(const int64_t* jobs, int n, int64_t rows, int64_t seq_len,
-                          const int64_t* lens, float* ws, hipStream_t st);
-int conv_wgrad_bf16_launch(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* slab,
-                           int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out, int taps,
-                           int pad, int splits, hipStream_t st);
+// the operands of one bf16 fs2_conv_wgrad call
+struct WgradCall {
+  const void* dy;
+  int64_t ldy;
+  const void* x;
+  int64_t ldx;
+  float* dw;
+  float* db;
+  int64_t rows, seq_len, c_in, c_out;
+  int taps, pad;
+  const int64_t* lens;
+  float* ws;
+};
+int conv_wgrad_bf16_launch(const WgradCall& c, hipStream_t st);
+int wgrad_k1_multi_bf16_launch(const int64_t* jobs, int n, int64_t rows, int64_t seq_len,
+                               const int64_t* lens, float* ws, hipStream_t st);
+// one launcher per weight-gradient kernel family: a plan to its template instance
+struct WgradPlan;
+int launch_wgrad_wide(const WgradPlan& p, const WgradCall& c, hipStream_t st);    // wgrad.hip
+int launch_wgrad_band(const WgradPlan& p, const WgradCall& c, hipStream_t st);    // wgrad_band.hip
+int launch_wgrad_k1_multi(const WgradPlan& p, const int64_t* jobs, int n, int64_t rows,
+                          int64_t seq_len, const int64_t* lens, float* ws, hipStream_t st);
+int launch_wgrad_splitk(const WgradPlan& p, const WgradCall& c, hipStream_t st);  // wgrad_splitk.hip
+int no_instance(const char* family);  // sets the error, returns FS2_ERR_LAUNCH
 int weight_prep_bf16_launch(const float* w, int64_t c_out, int64_t c_in, int taps, void* wf,
                             void* wb, hipStream_t st);
 int attn_fwd_bf16_launch(const void* qkv, void* o, float* lse, const int64_t* lens, int64_t batch,
@@ -180,17 +179,6 @@ FS2_DEV __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int64_t bytes) {
                                            (int)(bytes < 0x7fffffff ? bytes : 0x7fffffff), 0x00020000);
 }
 constexpr uint32_t kOOB = 0x80000000u;  // a voffset past every record count: reads zeros
-
-// Wait until at most `ahead` tiles of PER LDS-DMA instructions each are still in flight.
-template <int PER>
-FS2_DEV void vm_wait_tiles(int ahead) {
-  switch (ahead) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER) : "memory"); break;
-  }
-}
 
 // ------------------------------------------------------------------ Philox4x32-10
 struct u32x4 {

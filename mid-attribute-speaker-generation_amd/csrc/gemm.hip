@@ -10,6 +10,7 @@
 // consecutive k (two ds_read_b128) per fragment — the same lane->k pattern the bf16
 // 16x16x32 MFMA uses, so both share the LDS image.
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace fs2 {
 
@@ -384,34 +385,7 @@ int colsum_final_launch(const float* part, int64_t nparts, int64_t cols, float* 
   return launch_status("colsum_final");
 }
 
-// Weight-gradient decomposition (measured on the step's shapes, scripts/wgrad_sweep.py):
-// 128-wide tiles with <= 8 row splits for the large k>1 products, 64-wide tiles with 4..24
-// splits (>= 8 k-tiles of 64 rows each) for the small ones, ~1024 blocks where possible.
-static int wgrad_tile(int64_t rows, int64_t c_in, int64_t c_out, int taps) {
-  (void)rows;
-  if (g_tune[FS2_TUNE_WGRAD_TILE]) return g_tune[FS2_TUNE_WGRAD_TILE] == 64 ? 64 : 128;
-  return (int64_t)taps * c_in * c_out >= (1 << 20) ? 128 : 64;
-}
-
-static int wgrad_splits(int64_t rows, int64_t c_in, int64_t c_out, int taps) {
-  if (g_tune[FS2_TUNE_WGRAD_SPLITS]) {
-    const int s = g_tune[FS2_TUNE_WGRAD_SPLITS];
-    return s < 1 ? 1 : s > 64 ? 64 : s;
-  }
-  const int64_t Kp = (int64_t)taps * c_in;
-  const int bt = wgrad_tile(rows, c_in, c_out, taps);
-  const int64_t tiles = ((c_out + bt - 1) / bt) * ((Kp + bt - 1) / bt);
-  // k = 1 (tap-major kernel, 4 blocks per CU): at most one round of 1024 blocks -- rounding
-  // the split count up put 32 of the decoder QKV product's 1056 blocks in a second round
-  // (45.9 -> 33.6 us alone with 21 splits instead of 22)
-  int64_t s = taps == 1 ? 1024 / tiles : (1024 + tiles - 1) / tiles;
-  const int64_t hi = bt == 128 ? 8 : 24;
-  if (s > hi) s = hi;
-  if (s < 4) s = 4;
-  if (s > rows / 512) s = rows / 512;
-  if (s < 1) s = 1;
-  return (int)s;
-}
+static_assert(CS_ROWS == kColsumRows, "the planner's bias-partial rows");
 
 }  // namespace fs2
 
@@ -532,57 +506,22 @@ int fs2_conv_weight_prep(int dtype, const float* w, int64_t c_out, int64_t c_in,
   return launch_status("fs2_conv_weight_prep");
 }
 
-// workspace: split slabs [S][c_out][taps c_in], then the bias partials
+// workspace: split slabs [S][c_out][taps c_in], then the bias partials (conv_plan.hpp)
 int64_t fs2_conv_wgrad_ws_bytes(int64_t rows, int64_t c_in, int64_t c_out, int taps) {
-  const int64_t S = wgrad_splits(rows, c_in, c_out, taps);
-  const int64_t bias_part = S * c_out > ((rows + CS_ROWS - 1) / CS_ROWS) * c_out
-                                ? S * c_out : ((rows + CS_ROWS - 1) / CS_ROWS) * c_out;
-  int64_t b = (S * c_out * taps * c_in + bias_part) * 4;
-  const int64_t wide = conv_wgrad_wide_ws_floats(rows, c_in, c_out, taps) * 4;  // wgrad.hip
-  b = wide > b ? wide : b;
-  if (taps == 1) {  // bf16 k = 1: the grouped kernel with one job (wgrad.hip)
-    const int64_t job[8] = {0, c_out, 0, c_in, 0, 1, c_in, c_out};
-    const int64_t m = wgrad_k1_multi_ws_floats(job, 1, rows) * 4;
-    b = m > b ? m : b;
-  }
-  return b;
+  return wgrad_ws_bytes(rows, c_in, c_out, taps, g_tune);
 }
 
 int fs2_conv_wgrad(int dtype, const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw,
                    float* db, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out, int taps,
                    int pad, const int64_t* lens, float* ws, int64_t ws_bytes, void* stream) {
-  const int64_t slab_floats = (int64_t)wgrad_splits(rows, c_in, c_out, taps) * c_out * taps * c_in;
   if (dtype == FS2_BF16) {
     FS2_CHECK_ARG(ws_bytes >= fs2_conv_wgrad_ws_bytes(rows, c_in, c_out, taps),
                   "fs2_conv_wgrad: workspace too small");
     if (rows == 0) return FS2_OK;
     poison(ws, ws_bytes, as_stream(stream));
-    const int S = wgrad_splits(rows, c_in, c_out, taps);
-    if (taps == 1 && !g_tune[FS2_TUNE_LEGACY_GEMM] && g_tune[FS2_TUNE_WGRAD_K1] == 0) {
-      // k = 1: the grouped split-K kernel with one job (128 x 128 tiles, one reduce)
-      const int64_t job[8] = {(int64_t)dy, ldy, (int64_t)x, ldx, (int64_t)dw, (int64_t)db, c_in, c_out};
-      FS2_CHECK_ARG(c_in % 8 == 0 && c_out % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 &&
-                        ((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dw & 15) == 0,
-                    "fs2_conv_wgrad(bf16, k = 1): channel counts / strides must be multiples of 8, "
-                    "operands and dw 16-B aligned");
-      // the kernel reads lens[row / seq_len] to skip all-padding k-tiles
-      FS2_CHECK_ARG(lens == nullptr || (seq_len > 0 && rows % seq_len == 0),
-                    "fs2_conv_wgrad(bf16, k = 1): with lens, rows must be batch x seq_len");
-      return wgrad_k1_multi_launch(job, 1, rows, seq_len, lens, ws, as_stream(stream));
-    }
-    if (!g_tune[FS2_TUNE_LEGACY_GEMM])
-      return conv_wgrad_glds_launch(dy, ldy, x, ldx, dw, db, rows, seq_len, c_in, c_out, taps, pad,
-                                    lens, S, wgrad_tile(rows, c_in, c_out, taps), ws,
-                                    as_stream(stream));
-    int rc = conv_wgrad_bf16_launch(dy, ldy, x, ldx, ws, rows, seq_len, c_in, c_out, taps, pad, S,
-                                    as_stream(stream));
-    if (rc) return rc;
-    const int64_t total = c_out * c_in * taps;
-    unsigned blocks = (unsigned)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    wgrad_reduce<<<blocks, 256, 0, as_stream(stream)>>>(ws, S, (int)c_out, (int)c_in, taps, dw);
-    if (db) return colsum_bf16_launch(dy, ldy, rows, c_out, db, 1, ws + slab_floats, as_stream(stream));
-    return launch_status("fs2_conv_wgrad");
+    return conv_wgrad_bf16_launch(
+        WgradCall{dy, ldy, x, ldx, dw, db, rows, seq_len, c_in, c_out, taps, pad, lens, ws},
+        as_stream(stream));
   }
   if (dtype != FS2_F32) {
     set_error("fs2_conv_wgrad: dtype %d not built", dtype);
@@ -594,7 +533,8 @@ int fs2_conv_wgrad(int dtype, const void* dy, int64_t ldy, const void* x, int64_
                 "fs2_conv_wgrad: workspace too small");
   if (rows == 0) return FS2_OK;
   poison(ws, ws_bytes, as_stream(stream));
-  const int S = wgrad_splits(rows, c_in, c_out, taps);
+  const int S = wgrad_splits(rows, c_in, c_out, taps, g_tune);
+  const int64_t slab_floats = (int64_t)S * c_out * taps * c_in;
   int64_t rps = (rows + S - 1) / S;
   rps = (rps + BK - 1) / BK * BK;
   WgradArgs a{(const float*)dy, ldy, (const float*)x, ldx, ws, rows, seq_len, (int)c_in,
@@ -611,7 +551,7 @@ int fs2_conv_wgrad(int dtype, const void* dy, int64_t ldy, const void* x, int64_
 }
 
 int64_t fs2_conv_wgrad_k1_multi_ws_bytes(const int64_t* jobs, int n_jobs, int64_t rows) {
-  int64_t b = wgrad_k1_multi_ws_floats(jobs, n_jobs, rows) * 4;
+  int64_t b = wgrad_k1_multi_ws_floats(jobs, n_jobs, rows, g_tune) * 4;
   for (int j = 0; j < n_jobs; ++j) {  // the fp32 path runs the jobs one by one
     const int64_t w = fs2_conv_wgrad_ws_bytes(rows, jobs[8 * j + 6], jobs[8 * j + 7], 1);
     b = w > b ? w : b;
@@ -628,8 +568,8 @@ int fs2_conv_wgrad_k1_multi(int dtype, const int64_t* jobs, int n_jobs, int64_t 
   FS2_CHECK_ARG(seq_len > 0 && rows % seq_len == 0, "fs2_conv_wgrad_k1_multi: rows must be batch x seq_len");
   if (rows == 0) return FS2_OK;
   poison(ws, ws_bytes, as_stream(stream));
-  if (dtype == FS2_BF16 && !g_tune[FS2_TUNE_LEGACY_GEMM])
-    return wgrad_k1_multi_launch(jobs, n_jobs, rows, seq_len, lens, ws, as_stream(stream));
+  if (dtype == FS2_BF16)
+    return wgrad_k1_multi_bf16_launch(jobs, n_jobs, rows, seq_len, lens, ws, as_stream(stream));
   for (int j = 0; j < n_jobs; ++j) {
     const int64_t* r = jobs + 8 * j;
     const int rc = fs2_conv_wgrad(dtype, (const void*)r[0], r[1], (const void*)r[2], r[3],

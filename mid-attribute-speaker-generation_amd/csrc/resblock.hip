@@ -19,23 +19,15 @@
 // residual stream and bias / residual adds in the same order); only the MFMA summation order
 // differs.  Rows outside the tile's utterance are zero in every conv input (each Conv1d
 // zero-pads at the utterance edges), so a tile must lie inside one utterance (T % R == 0).
-#include "common.hpp"
+#include "glds.hpp"
 
 namespace fs2 {
 
 namespace {
 
-typedef __bf16 bf16x8r __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
 constexpr int RB_WAVES = 8;
 constexpr int RB_RAD = 64;  // max receptive radius per side (V1 k=11 chain: 3*5 + 5*(1+3+5) = 60)
 constexpr int RB_LD = 64;   // bf16 operand row: 64 elements = 128 B
-
-FS2_DEV u16 to_bf16(float f) {
-  __bf16 b = (__bf16)f;
-  return *reinterpret_cast<u16*>(&b);
-}
 
 FS2_DEV float lrelu(float v, float a) { return v >= 0.f ? v : a * v; }
 
@@ -71,17 +63,17 @@ constexpr int RB_FG = 4;  // row fragments per pass (independent accumulators)
 
 // the wave's weight slice for one conv: every k-step's A fragment, loaded once
 template <int C, int KT>
-FS2_DEV void rb_load_w(const u16* __restrict__ w, int wave, int lane, bf16x8r (&wr)[KT * (C / 32)]) {
+FS2_DEV void rb_load_w(const u16* __restrict__ w, int wave, int lane, bf16x8 (&wr)[KT * (C / 32)]) {
   constexpr int NB = C / 16, CH = C / 32;
   const int n = wave % NB;
   const u16* wl = w + (int64_t)(n * 16 + (lane & 15)) * (KT * C) + (lane >> 4) * 8;
 #pragma unroll
   for (int st = 0; st < KT * CH; ++st)
-    wr[st] = *reinterpret_cast<const bf16x8r*>(wl + (st / CH) * C + (st % CH) * 32);
+    wr[st] = *reinterpret_cast<const bf16x8*>(wl + (st / CH) * C + (st % CH) * 32);
 }
 
 template <int C, int R, int KT, typename Epi>
-FS2_DEV void rb_conv(const u16* in, bf16x8r (&wr)[KT * (C / 32)], const u16* w_next, int dil,
+FS2_DEV void rb_conv(const u16* in, bf16x8 (&wr)[KT * (C / 32)], const u16* w_next, int dil,
                      int pad, int E, int wave, int lane, Epi epi) {
   constexpr int NB = C / 16;            // output-channel slices
   constexpr int WPS = RB_WAVES / NB;    // waves per slice
@@ -108,7 +100,7 @@ FS2_DEV void rb_conv(const u16* in, bf16x8r (&wr)[KT * (C / 32)], const u16* w_n
         const int j = st / CH, ch = (st % CH) * 32 + kq * 8;
 #pragma unroll
         for (int g = 0; g < RB_FG; ++g) {
-          const bf16x8r x = *reinterpret_cast<const bf16x8r*>(in + op_index(base[g] + j * dil, ch));
+          const bf16x8 x = *reinterpret_cast<const bf16x8*>(in + op_index(base[g] + j * dil, ch));
           acc[g0 + g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[st], x, acc[g0 + g], 0, 0, 0);
         }
       }
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(RB_WAVES * 64, 1) void resblock1_fused(ResBlockArgs
     if (m0 - u * a.T >= a.lens[u]) continue;
   }
   const int64_t u0 = (m0 / a.T) * a.T, u1 = u0 + a.T < a.rows ? u0 + a.T : a.rows;
-  bf16x8r wr[KT * (C / 32)];
+  bf16x8 wr[KT * (C / 32)];
   rb_load_w<C, KT>(a.w1[0], wave, lane, wr);  // in flight under the tile load
   auto pack4 = [](float x0, float x1, float x2, float x3) {
     uint2 p;

@@ -1,392 +1,10 @@
-// Conv1d weight gradient without split-K slabs: conv_wgrad_band.
-//
-//   dw[o, c, j] += sum_r dy[r, o] * x[r + j - pad, c]        (taps 3 / 5 / 9)
-//   db[o]       += sum_r dy[r, o]
-//
-// Replaces the weight half of ConvolutionBackward for the FFT-block Conv1d FFN
-// (transformer/SubLayers.py:85-93), the PostNet convs (transformer/Layers.py:129-137) and the
-// variance-predictor convs (model/modules.py:209-250).
-//
-// The product is a tall reduction: 24,576 rows against a 1,024 x 2,304 output for the decoder
-// FFN.  The round-3 kernel split the rows over 8 blocks per output tile and round-tripped eight
-// fp32 slabs (72 MB written, 81 MB read back by a reduce launch, for a 9.4 MB result).  Here
-// one block owns a 32 (o) x 32 (c) x taps output tile for ALL rows, so the grid is the output
-// tiles (256 blocks for the decoder / encoder FFN and the PostNet 512 x 512 convs) and no slab
-// exists: the four waves of a block each take every fourth band of rows, hold the whole tile
-// in registers (taps x 2 x 2 fragments of v_mfma_f32_16x16x32_bf16), and are summed in a fixed
-// order through LDS at the end ((w0 + w2) + (w1 + w3): bitwise reproducible), then added
-// straight into dw / db.
-//
-// Bands.  A band is 32 S consecutive rows inside one utterance (T % 32 S == 0).  Its step s
-// (s < S) is the 32-deep MFMA reduction over the rows s + S m (m = 0..31), so tap j of step s
-// needs the input rows s + j + S m of the band's halo: halo fragment F[s + j], where F[f] are
-// the halo rows f + S m (f < S + taps - 1).  Each halo fragment is read from LDS ONCE and feeds
-// every (s, j) with s + j = f -- the tap-register idea of conv_gemm_tapreg applied to the
-// reduction dimension (rows may be paired with MFMA k-slots in any order, as long as dy and x
-// use the same one).  The dy image stores band row h at position (h mod S) * 32 + h / S and the
-// x image halo row h at (h mod S) * RS + h / S, so every fragment is 32 consecutive positions.
-// Positions are 64-B rows (32 bf16 columns); the 32-B halves swap at (P >> 2) & 1, which makes
-// the ds_read_b64_tr_b16 fragment reads conflict-free at any starting position.
-//
-// Each wave stages its own bands through its own ST-slot LDS ring by LDS-DMA and waits only for
-// its own loads (counted vmcnt): there is no barrier in the main loop.  Rows past an
-// utterance's length (lens given) are staged from the zero line, and bands made only of them
-// are not visited.  The bias gradient rides on the dy fragments of the blocks of the first c
-// tile (an MFMA against a ones fragment).
-#include <type_traits>
-
-#include "common.hpp"
+// Conv1d weight gradients on 64 x 64 x taps tiles shared by eight waves (conv_wgrad_wide) and the
+// grouped k = 1 weight gradient (wgrad_k1_multi) with the split reduce both use.  The slab-free
+// band kernel is in wgrad_band.hip.
+#include "glds.hpp"
+#include "conv_plan.hpp"
 
 namespace fs2 {
-
-typedef unsigned short u16;
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-typedef short s16x4w __attribute__((ext_vector_type(4)));
-
-
-struct WgradBand {
-  const u16* dy;
-  int64_t ldy;
-  const u16* x;
-  int64_t ldx;
-  float* dw;
-  float* db;
-  int64_t M, T;
-  int Cin, Cout, pad;
-  int tiles_o, tiles_c;
-  const int64_t* lens;
-};
-
-namespace {
-
-FS2_DEV void wb_glds16(const void* src, u16* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// ds_read_b64_tr_b16 as inline asm (invisible to the compiler's wait-count pass, which would
-// otherwise make every read wait for all LDS-DMA in flight); waited for with wb_lgkm<N>
-FS2_DEV s16x4w wb_tr16(const u16* p) {
-  s16x4w r;
-  const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) u16*)p;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(a));
-  return r;
-}
-template <int N>
-FS2_DEV void wb_lgkm() {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-FS2_DEV void wb_vm(int ahead) {  // at most `ahead` bands of N LDS-DMA instructions in flight
-  if (ahead <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  else if (ahead == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * N) : "memory");
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * N) : "memory");
-}
-
-}  // namespace
-
-namespace {
-template <int N, typename Fn>
-FS2_DEV void ww_static_for(Fn&& fn) {
-  if constexpr (N > 0) {
-    ww_static_for<N - 1>(fn);
-    fn(std::integral_constant<int, N - 1>{});
-  }
-}
-// ds_read_b64_tr_b16 at a per-lane base + a compile-time byte offset (the instruction's
-// 16-bit immediate): every fragment address of a main loop is one of a few per-lane bases
-template <int OFF>
-FS2_DEV s16x4w ww_tr(uint32_t base) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-  s16x4w r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(base), "n"(OFF));
-  return r;
-}
-FS2_DEV bf16x8w ww_cat(s16x4w lo, s16x4w hi) {
-  return __builtin_bit_cast(bf16x8w, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-}  // namespace
-
-template <int TAPS, int S, int ST, int W>
-__global__ __launch_bounds__(64 * W, W == 8 ? 1 : 2) void conv_wgrad_band(WgradBand a) {
-  constexpr int BO = 32, BC = 32, BR = 32 * S, NT = 64 * W;
-  constexpr int HR = BR + TAPS - 1, RS = (HR + S - 1) / S, NF = S + TAPS - 1;
-  constexpr int PB = 64;                                     // bytes per image position
-  constexpr int DPOS = BR, XPOS = (S * RS + 15) / 16 * 16;  // image positions
-  constexpr int NQD = DPOS / 16, NQX = XPOS / 16, NQ = NQD + NQX;  // LDS-DMA per band
-  constexpr int STAGE_B = (DPOS + XPOS) * PB;                     // bytes per ring slot
-  constexpr int RING_B = W * ST * STAGE_B;
-  static_assert(RING_B < 65536 + W * ST * STAGE_B, "offsets");
-  constexpr int QLD = BC * TAPS + 4;  // fp32 row stride of a dW-layout partial tile
-  constexpr int RED_B = (W / 2) * (BO * QLD * 4 + 2 * 64 * 16);  // W / 2 partial tiles + bias
-  static_assert(TAPS * 16 * 64 <= BO * QLD, "native partial fits a region");
-  constexpr int MAXB = 1024;
-  // the band list sits behind the ring, inside the reduction region (used after the main loop):
-  // 77 KB in all, two blocks per CU
-  constexpr int LIST_B = RING_B + 4 * MAXB + 64;
-  constexpr int SMEM_B = LIST_B > RED_B ? LIST_B : RED_B;
-  constexpr int LOOK = 2;  // halo fragments read ahead of their MFMAs
-  static_assert(NQ * (ST - 2 > 0 ? ST - 2 : 1) <= 63 && ST == 2, "vmcnt bookkeeping / the unrolled ring");
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM_B];
-  short* blist = reinterpret_cast<short*>(smem + RING_B);          // band index
-  short* brem = reinterpret_cast<short*>(smem + RING_B + 2 * MAXB);  // its rows below the length
-  int* wcnt = reinterpret_cast<int*>(smem + RING_B + 4 * MAXB);
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3, r16 = lane & 15;
-
-  // output tile: XCD-contiguous runs, c fastest (an XCD's blocks share their dy columns in L2)
-  const int nwg = a.tiles_o * a.tiles_c;
-  const int orig = blockIdx.x, xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-  const int to = wg / a.tiles_c, tc = wg - to * a.tiles_c;
-  const int o0 = to * BO, c0 = tc * BC;
-
-  // bands holding a real row, in row order, with their rows below the length (the launcher
-  // admits lens only with nb_all <= MAXB).  In LDS: a global load of lens in the main loop
-  // would make the compiler wait vmcnt(0) there, draining the LDS-DMA ring every band.
-  const int nbu = (int)(a.T / BR);
-  const int nb_all = (int)(a.M / BR);
-  const bool use_list = a.lens != nullptr;
-  int nb = nb_all;
-  if (use_list) {
-    int total = 0;
-    for (int k0 = 0; k0 < nb_all; k0 += NT) {
-      const int k = k0 + tid;
-      bool v = false;
-      int rem = 0;
-      if (k < nb_all) {
-        const int b = k / nbu;
-        const int64_t r = a.lens[b] - (int64_t)(k - b * nbu) * BR;
-        v = r > 0;
-        rem = r < BR ? (int)r : BR;
-      }
-      const uint64_t mask = __ballot(v);
-      if (lane == 0) wcnt[wave] = __popcll(mask);
-      __syncthreads();
-      int before = total;
-      for (int w = 0; w < wave; ++w) before += wcnt[w];
-      const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-      if (v) {
-        blist[before + below] = (short)k;
-        brem[before + below] = (short)rem;
-      }
-      for (int w = 0; w < W; ++w) total += wcnt[w];
-      __syncthreads();
-    }
-    nb = total;
-  }
-  const int nbw = nb > wave ? (nb - wave + W - 1) / W : 0;  // this wave: bands wave + W i
-
-  // the 32-B halves of position P swap at (P >> 2) & 1 (16-B chunk index ^ 2)
-  auto swz = [](int P) { return ((P >> 2) & 1) << 1; };
-  // LDS-DMA through buffer descriptors: dy from row 0, x from row -pad; the band's first row
-  // rides in the scalar offset
-  const auto dy_rs = buf_rsrc(a.dy, a.M * a.ldy * 2);
-  const auto x_rs = buf_rsrc(a.x - (int64_t)a.pad * a.ldx, (a.M + a.pad) * a.ldx * 2);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)smem;
-  unsigned char* ring = smem + wave * ST * STAGE_B;
-
-  auto issue = [&](int i, int slot) {
-    const int kk = wave + W * i;
-    const int k = __builtin_amdgcn_readfirstlane(use_list ? (int)blist[kk] : kk);
-    const int rem = __builtin_amdgcn_readfirstlane(use_list ? (int)brem[kk] : BR);
-    const int b = k / nbu, t0 = (k - b * nbu) * BR;
-    const int64_t r0 = (int64_t)b * a.T + t0;
-    unsigned char* St = ring + slot * STAGE_B;
-    // per-lane offsets recomputed here (an opaque lane id keeps them out of the registers
-    // held across the loop)
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    const int lpos = ln >> 2, lch = ln & 3;
-#pragma unroll
-    for (int qi = 0; qi < NQD; ++qi) {
-      const int P = qi * 16 + lpos;
-      const int h = (P & 31) * S + (P >> 5);
-      const int col = o0 + ((lch ^ swz(P)) << 3);
-      const bool ok = h < rem && col < a.Cout;
-      glds16_buf(dy_rs, St + qi * 16 * PB, ok ? (uint32_t)((h * a.ldy + col) * 2) : kOOB,
-                 (uint32_t)(r0 * a.ldy * 2));
-    }
-#pragma unroll
-    for (int qi = 0; qi < NQX; ++qi) {
-      const int P = qi * 16 + lpos;
-      const int h = (P % RS) * S + P / RS;
-      const int col = c0 + ((lch ^ swz(P)) << 3);
-      const int t = t0 - a.pad + h;
-      const bool ok = P < S * RS && h < HR && t >= 0 && t < (int)a.T && col < a.Cin;
-      glds16_buf(x_rs, St + (DPOS + qi * 16) * PB, ok ? (uint32_t)((h * a.ldx + col) * 2) : kOOB,
-                 (uint32_t)(r0 * a.ldx * 2));
-    }
-  };
-
-  f32x4 acc[TAPS][2][2], accb[2];
-#pragma unroll
-  for (int j = 0; j < TAPS; ++j)
-#pragma unroll
-    for (int io = 0; io < 2; ++io)
-#pragma unroll
-      for (int ic = 0; ic < 2; ++ic) acc[j][io][ic] = f32x4{0.f, 0.f, 0.f, 0.f};
-  accb[0] = accb[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool do_bias = a.db != nullptr && tc == 0;  // block-uniform
-  bf16x8w ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-
-  // per-lane fragment bases: the fragment of 32 positions from pb (rows pb + 4g + q and + 16),
-  // 16 columns at col0, reads base(pb mod 8, col0) + (pb - pb mod 8) PB (+ 16 PB): the swizzle
-  // of position pb + L depends on pb only through pb mod 8
-  const int L = 4 * g + q;
-  auto fbase = [&](int r, int col0, int img) -> uint32_t {
-    const int lc = (col0 >> 3) + (p >> 1);
-    return lds0 + (uint32_t)(wave * ST * STAGE_B + img + (r + L) * PB + ((lc ^ swz(r + L)) << 4) +
-                             ((p & 1) << 3));
-  };
-  uint32_t bA0 = fbase(0, 0, 0), bA1 = fbase(0, 16, 0);
-  uint32_t bF[8][2];
-#pragma unroll
-  for (int r = 0; r < 8; ++r)
-#pragma unroll
-    for (int ic = 0; ic < 2; ++ic) bF[r][ic] = fbase(r, ic * 16, DPOS * PB);
-
-  auto compute = [&](auto slot_c) {
-    constexpr int SO = decltype(slot_c)::value * STAGE_B;
-    bf16x8w A[S][2], F[LOOK + 1][2];
-    ww_static_for<S>([&](auto sc) {
-      constexpr int s = decltype(sc)::value;
-      A[s][0] = ww_cat(ww_tr<SO + s * 32 * PB>(bA0), ww_tr<SO + (s * 32 + 16) * PB>(bA0));
-      A[s][1] = ww_cat(ww_tr<SO + s * 32 * PB>(bA1), ww_tr<SO + (s * 32 + 16) * PB>(bA1));
-    });
-    auto rdF = [&](auto fc, bf16x8w (&dst)[2]) {
-      constexpr int f = decltype(fc)::value;
-      constexpr int pb = (f % S) * RS + f / S, r = pb & 7, off = SO + (pb - r) * PB;
-      dst[0] = ww_cat(ww_tr<off>(bF[r][0]), ww_tr<off + 16 * PB>(bF[r][0]));
-      dst[1] = ww_cat(ww_tr<off>(bF[r][1]), ww_tr<off + 16 * PB>(bF[r][1]));
-    };
-    ww_static_for<LOOK>([&](auto fc) { rdF(fc, F[decltype(fc)::value]); });
-    ww_static_for<NF>([&](auto fc) {
-      constexpr int f = decltype(fc)::value;
-      if constexpr (f + LOOK < NF) rdF(std::integral_constant<int, f + LOOK>{}, F[(f + LOOK) % (LOOK + 1)]);
-      constexpr int younger = (NF - 1 - f < LOOK ? NF - 1 - f : LOOK) * 4;
-      wb_lgkm<younger>();
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const int j = f - s;
-        if (j < 0 || j >= TAPS) continue;
-#pragma unroll
-        for (int io = 0; io < 2; ++io)
-#pragma unroll
-          for (int ic = 0; ic < 2; ++ic)
-            acc[j][io][ic] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[s][io], F[f % (LOOK + 1)][ic],
-                                                                     acc[j][io][ic], 0, 0, 0);
-        if (j == 0 && do_bias) {
-#pragma unroll
-          for (int io = 0; io < 2; ++io)
-            accb[io] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[s][io], ones, accb[io], 0, 0, 0);
-        }
-      }
-    });
-  };
-
-  // per-wave 2-slot ring, no barrier: wait for this wave's band i (counted vmcnt), refill the
-  // other slot with band i + 1, compute band i; the fragment bases step to the other slot
-  // after each band (one add per base)
-  if (nbw > 0) issue(0, 0);
-  int dslot = STAGE_B;
-  for (int i = 0; i < nbw; ++i) {
-    wb_vm<NQ>(0);
-    if (i + 1 < nbw) issue(i + 1, (i + 1) & 1);
-    compute(std::integral_constant<int, 0>{});
-    bA0 += dslot;
-    bA1 += dslot;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      bF[r][0] += dslot;
-      bF[r][1] += dslot;
-    }
-    dslot = -dslot;
-  }
-
-  // fixed-order cross-wave sum, a tree through LDS: waves [h, 2h) write their partials, waves
-  // [0, h) add them (h = W/2, ..., 2), so wave 0 holds (p0 + p4) + (p2 + p6) and wave 1 the
-  // odd pairs (W = 8); both write their sums in the dw layout ([o][c][j], row stride QLD) and
-  // every thread adds the two into dw / db
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  float* Q = reinterpret_cast<float*>(smem);
-  f32x4* QB = reinterpret_cast<f32x4*>(Q + (W / 2) * BO * QLD);  // [W / 2][2 io][64 lanes]
-#pragma unroll
-  for (int h = W / 2; h >= 2; h /= 2) {
-    if (wave >= h && wave < 2 * h) {
-      f32x4* dst = reinterpret_cast<f32x4*>(Q + (wave - h) * BO * QLD);
-#pragma unroll
-      for (int j = 0; j < TAPS; ++j)
-#pragma unroll
-        for (int io = 0; io < 2; ++io)
-#pragma unroll
-          for (int ic = 0; ic < 2; ++ic) dst[((j * 2 + io) * 2 + ic) * 64 + lane] = acc[j][io][ic];
-      if (do_bias) {
-        QB[((wave - h) * 2 + 0) * 64 + lane] = accb[0];
-        QB[((wave - h) * 2 + 1) * 64 + lane] = accb[1];
-      }
-    }
-    __syncthreads();
-    if (wave < h) {
-      const f32x4* src = reinterpret_cast<const f32x4*>(Q + wave * BO * QLD);
-#pragma unroll
-      for (int j = 0; j < TAPS; ++j)
-#pragma unroll
-        for (int io = 0; io < 2; ++io)
-#pragma unroll
-          for (int ic = 0; ic < 2; ++ic) acc[j][io][ic] += src[((j * 2 + io) * 2 + ic) * 64 + lane];
-      if (do_bias) {
-        accb[0] += QB[(wave * 2 + 0) * 64 + lane];
-        accb[1] += QB[(wave * 2 + 1) * 64 + lane];
-      }
-    }
-    __syncthreads();
-  }
-  if (wave < 2) {
-    float* dst = Q + wave * BO * QLD;
-#pragma unroll
-    for (int j = 0; j < TAPS; ++j)
-#pragma unroll
-      for (int io = 0; io < 2; ++io)
-#pragma unroll
-        for (int ic = 0; ic < 2; ++ic)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            dst[(io * 16 + 4 * g + r) * QLD + (ic * 16 + r16) * TAPS + j] = acc[j][io][ic][r];
-    if (do_bias && r16 == 0) {
-#pragma unroll
-      for (int io = 0; io < 2; ++io)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) QB[(wave * 2 + io) * 64 + 4 * g + r][0] = accb[io][r];
-    }
-  }
-  __syncthreads();
-  {
-    constexpr int V = BC * TAPS / 4;  // f32x4 per output row of the tile
-    const int64_t Kp = (int64_t)a.Cin * TAPS;
-    const int ncol = (a.Cin - c0 < BC ? a.Cin - c0 : BC) * TAPS;  // valid floats per row
-    for (int e = tid; e < BO * V; e += NT) {
-      const int o = e / V, v4 = e - o * V;
-      if (o0 + o >= a.Cout || 4 * v4 >= ncol) continue;
-      const f32x4 s = ld4(Q + o * QLD + 4 * v4) + ld4(Q + BO * QLD + o * QLD + 4 * v4);
-      float* d = a.dw + (int64_t)(o0 + o) * Kp + (int64_t)c0 * TAPS + 4 * v4;
-      st4(d, ld4(d) + s);
-    }
-    if (do_bias && tid < BO && o0 + tid < a.Cout) {
-      const int io = tid >> 4, gg = (tid & 15) >> 2, r = tid & 3;
-      const float b = QB[(0 * 2 + io) * 64 + 4 * gg + r][0] + QB[(1 * 2 + io) * 64 + 4 * gg + r][0];
-      a.db[o0 + tid] += b;
-    }
-  }
-}
 
 // ---------------------------------------------------------------- wide-tile weight gradient
 // conv_wgrad_wide: the same product on 64 (o) x 64 (c) x taps output tiles, the rows split Z
@@ -427,7 +45,6 @@ struct WgradWide {
   int tiles_o, tiles_c, Z;
   const int64_t* lens;
 };
-
 
 template <int TAPS, int ST>
 __global__ __launch_bounds__(512, 4) void conv_wgrad_wide(WgradWide a) {
@@ -621,27 +238,24 @@ __global__ __launch_bounds__(512, 4) void conv_wgrad_wide(WgradWide a) {
 
   auto compute = [&](auto slot_c) {
     constexpr int SO = decltype(slot_c)::value * STAGE_B;
-    auto cat = [](s16x4w lo, s16x4w hi) {
-      return __builtin_bit_cast(bf16x8w, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-    bf16x8w A[S][2], F[LOOK + 1];
-    ww_static_for<S>([&](auto sc) {
+    bf16x8 A[S][2], F[LOOK + 1];
+    static_for<S>([&](auto sc) {
       constexpr int s = decltype(sc)::value;
-      A[s][0] = cat(ww_tr<SO + s * 32 * PB>(bA0), ww_tr<SO + (s * 32 + 16) * PB>(bA0));
-      A[s][1] = cat(ww_tr<SO + s * 32 * PB>(bA1), ww_tr<SO + (s * 32 + 16) * PB>(bA1));
+      A[s][0] = tr16_cat(ds_tr16_at<SO + s * 32 * PB>(bA0), ds_tr16_at<SO + (s * 32 + 16) * PB>(bA0));
+      A[s][1] = tr16_cat(ds_tr16_at<SO + s * 32 * PB>(bA1), ds_tr16_at<SO + (s * 32 + 16) * PB>(bA1));
     });
-    auto rdF = [&](auto fc) -> bf16x8w {
+    auto rdF = [&](auto fc) -> bf16x8 {
       constexpr int f = decltype(fc)::value;
       constexpr int pb = (f % S) * RS + f / S, r = pb & 7, off = SO + (pb - r) * PB;
-      return cat(ww_tr<off>(bF[r]), ww_tr<off + 16 * PB>(bF[r]));
+      return tr16_cat(ds_tr16_at<off>(bF[r]), ds_tr16_at<off + 16 * PB>(bF[r]));
     };
-    ww_static_for<LOOK>([&](auto fc) { F[decltype(fc)::value] = rdF(fc); });
-    ww_static_for<NF>([&](auto fc) {
+    static_for<LOOK>([&](auto fc) { F[decltype(fc)::value] = rdF(fc); });
+    static_for<NF>([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       if constexpr (f + LOOK < NF) F[(f + LOOK) % (LOOK + 1)] = rdF(std::integral_constant<int, f + LOOK>{});
       constexpr int younger = (NF - 1 - f < LOOK ? NF - 1 - f : LOOK) * 2;
-      wb_lgkm<younger>();
-      const bf16x8w Ff = F[f % (LOOK + 1)];
+      lgkm_wait<younger>();
+      const bf16x8 Ff = F[f % (LOOK + 1)];
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         const int j = f - s;
@@ -709,44 +323,6 @@ __global__ __launch_bounds__(512, 4) void conv_wgrad_wide(WgradWide a) {
   }
 }
 
-// kNotEligible: the caller uses the split-K kernels
-int conv_wgrad_band_launch(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw,
-                           float* db, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out,
-                           int taps, int pad, const int64_t* lens, hipStream_t st) {
-  const int S = 2, BR = 32 * S;
-  if (!(taps == 3 || taps == 5 || taps == 9)) return kNotEligible;
-  if (pad < 0 || pad > taps - 1) return kNotEligible;
-  if (c_in % 8 || c_out % 8 || ldx % 8 || ldy % 8 || ((uintptr_t)dy & 15) || ((uintptr_t)x & 15))
-    return kNotEligible;
-  if (seq_len % BR || rows % seq_len || rows / BR > (1 << 15)) return kNotEligible;
-  if (lens && rows / BR > 1024) return kNotEligible;  // the kernel's LDS band list
-  if (c_in < 32 || c_out < 32) return kNotEligible;
-  // taps 3 / 5 with 64-multiple channels (PostNet 512, variance predictors) stay on the split-K
-  // halo kernel: step 6.91 vs 6.98 ms with the band kernel there (profiles/r4_ab_experiments.txt)
-  if (g_tune[FS2_TUNE_WGRAD_BAND] != 4 && taps != 9 && c_in % 64 == 0 && c_out % 64 == 0 &&
-      seq_len % 64 == 0)
-    return kNotEligible;
-  const int to = (int)((c_out + 31) / 32), tc = (int)((c_in + 31) / 32);
-  // grids under half the CUs keep the split-K kernels (the variance predictors' 256 x 256 k=3
-  // convs at T = 128: 64 tiles), unless those would be the tap-major kernel (C % 64 != 0: the
-  // PostNet's 80-channel convs, 48 tiles -- 26 vs 47 us alone, on 48 CUs)
-  const bool halo_ok = c_in % 64 == 0 && c_out % 64 == 0 && seq_len % 64 == 0;
-  const int min_tiles = g_tune[FS2_TUNE_WGRAD_BAND] == 3 ? 128 : halo_ok ? 128 : 32;
-  if (to * tc < min_tiles) return kNotEligible;
-  // f32x4 read-modify-writes of dw: rows of c_in * taps floats, tile columns 32 * taps
-  if (((uintptr_t)dw & 15) || (c_in * taps) % 4) return kNotEligible;
-  WgradBand a{(const u16*)dy, ldy, (const u16*)x, ldx, dw, db, rows, seq_len, (int)c_in,
-              (int)c_out, pad, to, tc, lens};
-  const unsigned grid = (unsigned)(to * tc);
-  // (4-slot rings and 8-wave blocks measured slower in the step and were removed in round 5:
-  // profiles/r4_ab_experiments.txt)
-  if (taps == 9) conv_wgrad_band<9, 2, 2, 4><<<grid, 256, 0, st>>>(a);
-  else if (taps == 5) conv_wgrad_band<5, 2, 2, 4><<<grid, 256, 0, st>>>(a);
-  else conv_wgrad_band<3, 2, 2, 4><<<grid, 256, 0, st>>>(a);
-  return launch_status("fs2_conv_wgrad(bf16, band)");
-}
-
-
 // ---------------------------------------------------------------- grouped k = 1 weight gradient
 // wgrad_k1_multi: the k = 1 weight gradients of one FFT block -- QKV (768 x 256 + bias), fc
 // (256 x 256) and w_2 (256 x 1024) at the decoder shapes, transformer/SubLayers.py:39-55,88 --
@@ -782,16 +358,6 @@ struct K1Multi {
   int64_t M, T;
   const int64_t* lens;
 };
-
-namespace {
-FS2_DEV bool wb_rows_all_padding(const int64_t* lens, int64_t T, int64_t r0, int64_t r1) {
-  int64_t s = r0 / T;
-  if (r0 - s * T < lens[s]) return false;
-  for (++s; s * T < r1; ++s)
-    if (lens[s] > 0) return false;
-  return true;
-}
-}  // namespace
 
 template <int STAGES>
 __global__ __launch_bounds__(512, 1) void wgrad_k1_multi(K1Multi m) {
@@ -840,7 +406,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_k1_multi(K1Multi m) {
       bool v = false;
       if (kt < nk_all) {
         const int64_t k0 = r_begin + (int64_t)kt * BK;
-        v = !wb_rows_all_padding(m.lens, m.T, k0, k0 + BK < r_end ? k0 + BK : r_end);
+        v = !rows_all_padding(m.lens, m.T, k0, k0 + BK < r_end ? k0 + BK : r_end);
       }
       const uint64_t mask = __ballot(v);
       if (lane == 0) wcnt[wave] = __popcll(mask);
@@ -896,21 +462,18 @@ __global__ __launch_bounds__(512, 1) void wgrad_k1_multi(K1Multi m) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const bool do_bias = J.db != nullptr && tc == 0 && (quad & 1) == 0;  // wave-uniform
-  bf16x8w ones;
+  bf16x8 ones;
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
   const int rbase = half * 32 + 4 * g + q, sw = swz(rbase);
-  auto tr = [&](const u16* img, int col0, int hi) -> s16x4w {
+  auto tr = [&](const u16* img, int col0, int hi) -> s16x4 {
     const int lc = (col0 >> 3) + (p >> 1);
-    return wb_tr16(img + (rbase + 16 * hi) * 128 + ((lc ^ sw) << 3) + ((p & 1) << 2));
-  };
-  auto cat = [](s16x4w lo, s16x4w hi) {
-    return __builtin_bit_cast(bf16x8w, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    return ds_tr16(img + (rbase + 16 * hi) * 128 + ((lc ^ sw) << 3) + ((p & 1) << 2));
   };
   auto compute = [&](int stage) {
     const u16* As = smem + stage * STAGE_E;
     const u16* Bs = As + IMG;
-    s16x4w ra[4][2], rb[4][2];
+    s16x4 ra[4][2], rb[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       ra[i][0] = tr(As, qo + i * 16, 0);
@@ -921,20 +484,20 @@ __global__ __launch_bounds__(512, 1) void wgrad_k1_multi(K1Multi m) {
       rb[j][0] = tr(Bs, qc + j * 16, 0);
       rb[j][1] = tr(Bs, qc + j * 16, 1);
     }
-    bf16x8w fa[4];
+    bf16x8 fa[4];
     // c fragment j's MFMAs wait only for the reads up to it (4-bit counter: the 16th read
     // issues once the first has retired, so 6 - 2 j younger reads remain in flight)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (j == 0) wb_lgkm<6>();
-      else if (j == 1) wb_lgkm<4>();
-      else if (j == 2) wb_lgkm<2>();
-      else wb_lgkm<0>();
+      if (j == 0) lgkm_wait<6>();
+      else if (j == 1) lgkm_wait<4>();
+      else if (j == 2) lgkm_wait<2>();
+      else lgkm_wait<0>();
       if (j == 0) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i] = cat(ra[i][0], ra[i][1]);
+        for (int i = 0; i < 4; ++i) fa[i] = tr16_cat(ra[i][0], ra[i][1]);
       }
-      const bf16x8w fb = cat(rb[j][0], rb[j][1]);
+      const bf16x8 fb = tr16_cat(rb[j][0], rb[j][1]);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb, acc[i][j], 0, 0, 0);
@@ -1064,43 +627,18 @@ __global__ __launch_bounds__(256) void wgrad_k1_multi_reduce(K1Red r) {
   r.db[j][o] += acc;
 }
 
-// jobs: host int64 rows {dy, ldy, x, ldx, dw, db, c_in, c_out}; splits chosen so that the grid
-// is about 256 blocks of 128 x 128 tiles
-static int k1_multi_splits(int64_t tiles_total, int64_t rows) {
-  int64_t s = (256 + tiles_total / 2) / tiles_total;
-  if (s > rows / 512) s = rows / 512;  // >= 8 k-tiles per split (small products: fewer slabs)
-  return (int)(s < 1 ? 1 : s);
-}
-
-int64_t wgrad_k1_multi_ws_floats(const int64_t* jobs, int n, int64_t rows) {
-  int64_t tiles = 0;
-  for (int j = 0; j < n; ++j) {
-    const int64_t cin = jobs[8 * j + 6], cout = jobs[8 * j + 7];
-    tiles += ((cout + 127) / 128) * ((cin + 127) / 128);
-  }
-  const int S = k1_multi_splits(tiles > 0 ? tiles : 1, rows);
-  int64_t f = 0;
-  for (int j = 0; j < n; ++j) {
-    const int64_t cin = jobs[8 * j + 6], cout = jobs[8 * j + 7];
-    f += S * cout * cin + (jobs[8 * j + 5] ? S * cout : 0);
-    f = (f + 3) / 4 * 4;
-  }
-  return f;
-}
-
-int wgrad_k1_multi_launch(const int64_t* jobs, int n, int64_t rows, int64_t seq_len,
-                          const int64_t* lens, float* ws, hipStream_t st) {
+// jobs: host int64 rows {dy, ldy, x, ldx, dw, db, c_in, c_out}; p = plan_wgrad_k1_multi of them
+int launch_wgrad_k1_multi(const WgradPlan& p, const int64_t* jobs, int n, int64_t rows,
+                          int64_t seq_len, const int64_t* lens, float* ws, hipStream_t st) {
   FS2_CHECK_ARG(n >= 1 && n <= K1_MAXJ, "fs2_conv_wgrad_k1_multi: 1..%d jobs", K1_MAXJ);
-  int64_t tiles = 0;
   for (int j = 0; j < n; ++j) {
     const int64_t* r = jobs + 8 * j;
     FS2_CHECK_ARG(r[6] % 8 == 0 && r[7] % 8 == 0 && r[1] % 8 == 0 && r[3] % 8 == 0 &&
                       (r[0] & 15) == 0 && (r[2] & 15) == 0 && (r[4] & 15) == 0,
                   "fs2_conv_wgrad_k1_multi: channel counts / strides must be multiples of 8, "
                   "operands 16-B aligned");
-    tiles += ((r[7] + 127) / 128) * ((r[6] + 127) / 128);
   }
-  const int S = k1_multi_splits(tiles, rows);
+  const int S = p.splits;
   int64_t rps = (rows + S - 1) / S;
   rps = (rps + 63) / 64 * 64;
   for (int j = 0; j < n; ++j) {
@@ -1151,80 +689,49 @@ int wgrad_k1_multi_launch(const int64_t* jobs, int n, int64_t rows, int64_t seq_
   red.u_begin[n] = ub;
   red.b_begin[n] = bb;
   m.nblocks = begin;
-  // LDS ring depth (FS2_TUNE_WGRAD_K1M_STAGES, A/B): 0 = 4 slots (128 KB, three k-tiles in flight)
-  const int stg = g_tune[FS2_TUNE_WGRAD_K1M_STAGES];
-  if (stg == 2) wgrad_k1_multi<2><<<(unsigned)begin, 512, 0, st>>>(m);
-  else if (stg == 3) wgrad_k1_multi<3><<<(unsigned)begin, 512, 0, st>>>(m);
-  else wgrad_k1_multi<4><<<(unsigned)begin, 512, 0, st>>>(m);
-  wgrad_k1_multi_reduce<<<(unsigned)((ub + bb + 255) / 256), 256, 0, st>>>(red);
-  return launch_status("fs2_conv_wgrad_k1_multi");
+  if ((unsigned)begin != p.grid) return no_instance("wgrad_k1_multi (grid)");  // the plan's tiles x splits
+  if (p.stages == 2) wgrad_k1_multi<2><<<p.grid, 512, 0, st>>>(m);
+  else if (p.stages == 3) wgrad_k1_multi<3><<<p.grid, 512, 0, st>>>(m);
+  else wgrad_k1_multi<4><<<p.grid, 512, 0, st>>>(m);
+  wgrad_k1_multi_reduce<<<p.reduce_grid, 256, 0, st>>>(red);
+  return FS2_OK;
 }
 
 // ---------------------------------------------------------------- wide-tile launcher
-// split count: about 256 blocks, >= 4 bands per split (FS2_TUNE_WGRAD_WIDE > 1 forces it);
-// 0 = not eligible
-int conv_wgrad_wide_splits(int64_t rows, int64_t c_in, int64_t c_out, int taps) {
-  const int v = g_tune[FS2_TUNE_WGRAD_WIDE];
-  if (v < 0) return 0;
-  if (!(taps == 3 || taps == 5 || taps == 9)) return 0;
-  // default: the channel counts that are not 64-multiples (the PostNet's 80-channel convs:
-  // 97.5 -> 36 us alone against the band kernel).  On the 64-multiple shapes it was neutral to
-  // slower alone and 0.54 ms/step slower in the step (its 163-VGPR waves, two per SIMD, leave
-  // no room for the concurrent data gradient's 244-VGPR waves; profiles/r5_wide_ab.txt)
-  if (v == 0 && c_in % 64 == 0 && c_out % 64 == 0) return 0;
-  if (rows % 64 || rows / 64 > (1 << 15) || rows < 256) return 0;
-  if (c_in % 8 || c_out % 8 || (c_in * taps) % 4) return 0;
-  const int64_t tiles = ((c_out + 63) / 64) * ((c_in + 63) / 64);
-  const int64_t nb = rows / 64;
-  int64_t z = g_tune[FS2_TUNE_WGRAD_WIDE] > 1 ? g_tune[FS2_TUNE_WGRAD_WIDE] : (256 + tiles / 2) / tiles;
-  if (z > nb / 4) z = nb / 4;
-  if (z > 64) z = 64;
-  return (int)(z < 1 ? 1 : z);
+static_assert(WIDE_MAXB == kWideMaxBands, "the planner's limit of conv_wgrad_wide");
+
+template <int TAPS>
+static bool wide_try(const WgradPlan& p, const WgradWide& a, hipStream_t st) {
+  if (p.taps != TAPS) return false;
+  conv_wgrad_wide<TAPS, 3><<<p.grid, 512, 0, st>>>(a);
+  return true;
 }
 
-// slab workspace (floats) the wide kernel needs at this shape (0 when it needs none)
-int64_t conv_wgrad_wide_ws_floats(int64_t rows, int64_t c_in, int64_t c_out, int taps) {
-  const int z = conv_wgrad_wide_splits(rows, c_in, c_out, taps);
-  if (z <= 1) return 0;
-  return (int64_t)z * c_out * (c_in * taps + 1);
-}
-
-// kNotEligible: the caller uses the other kernels
-int conv_wgrad_wide_launch(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw,
-                           float* db, int64_t rows, int64_t seq_len, int64_t c_in, int64_t c_out,
-                           int taps, int pad, const int64_t* lens, float* ws, hipStream_t st) {
-  const int Z = conv_wgrad_wide_splits(rows, c_in, c_out, taps);
-  if (Z < 1 || seq_len <= 0 || seq_len % 64 || rows % seq_len) return kNotEligible;
-  if (lens && rows / 64 > WIDE_MAXB) return kNotEligible;
-  if (pad < 0 || pad > taps - 1) return kNotEligible;
-  if (ldx % 8 || ldy % 8 || ((uintptr_t)dy & 15) || ((uintptr_t)x & 15) || ((uintptr_t)dw & 15))
-    return kNotEligible;
-  if (Z > 1 && (ws == nullptr || ((uintptr_t)ws & 15))) return kNotEligible;
-  const int to = (int)((c_out + 63) / 64), tc = (int)((c_in + 63) / 64);
-  const int64_t Kp = c_in * taps;
-  float* bslab = (Z > 1 && db) ? ws + (int64_t)Z * c_out * Kp : nullptr;
-  WgradWide a{(const u16*)dy, ldy, (const u16*)x, ldx, dw, db, Z > 1 ? ws : nullptr, bslab,
-              rows, seq_len, (int)c_in, (int)c_out, pad, to, tc, Z, lens};
-  const unsigned grid = (unsigned)(to * tc * Z + (db ? Z * to : 0));
-  if (taps == 9) conv_wgrad_wide<9, 3><<<grid, 512, 0, st>>>(a);
-  else if (taps == 5) conv_wgrad_wide<5, 3><<<grid, 512, 0, st>>>(a);
-  else conv_wgrad_wide<3, 3><<<grid, 512, 0, st>>>(a);
+// splits > 1: split slabs and bias partials in ws, summed by wgrad_k1_multi_reduce
+int launch_wgrad_wide(const WgradPlan& p, const WgradCall& c, hipStream_t st) {
+  const int Z = p.splits;
+  const int64_t Kp = c.c_in * c.taps;
+  float* bslab = (Z > 1 && c.db) ? c.ws + (int64_t)Z * c.c_out * Kp : nullptr;
+  const WgradWide a{(const u16*)c.dy, c.ldy, (const u16*)c.x, c.ldx, c.dw, c.db,
+                    Z > 1 ? c.ws : nullptr, bslab, c.rows, c.seq_len, (int)c.c_in, (int)c.c_out,
+                    c.pad, p.tiles_o, p.tiles_k, Z, c.lens};
+  const bool ok = wide_try<9>(p, a, st) || wide_try<5>(p, a, st) || wide_try<3>(p, a, st);
+  if (!ok) return no_instance("conv_wgrad_wide");
   if (Z > 1) {
     K1Red red{};
     red.n = 1;
-    red.slab[0] = ws;
+    red.slab[0] = c.ws;
     red.bslab[0] = bslab;
-    red.dw[0] = dw;
-    red.db[0] = db;
+    red.dw[0] = c.dw;
+    red.db[0] = c.db;
     red.splits[0] = Z;
     red.u_begin[0] = 0;
-    red.u_begin[1] = c_out * Kp / 4;
+    red.u_begin[1] = c.c_out * Kp / 4;
     red.b_begin[0] = 0;
-    red.b_begin[1] = db ? c_out : 0;
-    const int64_t n = red.u_begin[1] + red.b_begin[1];
-    wgrad_k1_multi_reduce<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(red);
+    red.b_begin[1] = c.db ? c.c_out : 0;
+    wgrad_k1_multi_reduce<<<p.reduce_grid, 256, 0, st>>>(red);
   }
-  return launch_status("fs2_conv_wgrad(bf16, wide)");
+  return FS2_OK;
 }
 
 }  // namespace fs2

@@ -480,7 +480,7 @@ def test_conv_gemm_ex_lens(c_in, c_out, taps, dil, pad, epi, out_kind, with_y2, 
        FS2_EPI_SKIP_NOSTORE the buffer's earlier contents, else the epilogue of a zero
        accumulator without bias (aux under ADD_AUX, then ACC_Y, scale, LRELU; y2 of that);
     3. the skip happens: the tallest row tile of these kernels is 256 rows
-       (conv_gemm_halo<256, 128, ...> in csrc/gemm_glds.hip's conv_gemm_glds_launch; the
+       (conv_gemm_halo<256, 128, ...> in csrc/gemm_glds.hip, chosen by csrc/conv_plan.hpp; the
        vocoder instantiations use 128 and 64), so any tiling puts rows [768, 1024) of
        utterance 1 and [256, 768) of utterance 2 in all-padding tiles;
     4. the fp32 path ignores lens."""
