@@ -285,6 +285,42 @@ int fs2_ge2e_eer(const float* enroll, const float* verify, int64_t n_spk, int64_
  * logit are each nullable (their total then stays); correct (nullable) receives the count.   */
 int fs2_epoch_stats_add(float* totals, const float* loss, const float* da_loss, const float* logit,
                         const float* y, int64_t n, float* correct, void* stream);
+/* The FastSpeech2 training batch cut on the device from a device-resident corpus: what
+ * Dataset.reprocess + to_device build on the host (dataset.py:112-172, utils/tools.py:18-125).
+ * The corpus is one flat store per field, utterance after utterance: text, dur, accent (int64,
+ * src_len[u] entries at element src_off[u]), mel (fp32, mel_len[u] * n_mels entries at element
+ * mel_off[u], a multiple of n_mels), pitch (fp32) and energy (energy_bytes = 4: fp32, 8: fp64),
+ * each at src_off[u] with src_len[u] entries, or -- *_frame != 0 -- at frame mel_off[u] / n_mels
+ * with mel_len[u] entries; meta (n_utt, meta_dim) fp32 and speaker (n_utt) int64.
+ * idx: device int32[batch], the utterances of the batch in row order.  Outputs, row b from
+ * utterance idx[b], zero past the utterance's length (pad_1D / pad_2D): o_text, o_dur, o_accent
+ * (batch, max_src_len) int64; o_mel (batch, max_mel_len, n_mels); o_pitch / o_energy (batch,
+ * max_src_len), or (batch, max_mel_len) when frame-level, in their store type; o_src_len,
+ * o_mel_len, o_speaker (batch) int64; o_meta (batch, meta_dim).  accent and o_accent are
+ * nullable (a 13-tuple batch has no accents).  One launch; every output element is written.
+ * Host-side validation before anything is launched or touched (FS2_ERR_ARG): the caller passes
+ * HOST copies of the indices (idx_host) and of the two length tables (src_len_host,
+ * mel_len_host, int32[n_utt]); batch >= 1, every index in 0..n_utt-1, max_src_len / max_mel_len
+ * >= the lengths of every utterance of the batch (larger is allowed: data-parallel shards pad to
+ * the ranks' maxima), non-null pointers, n_mels a multiple of 4 and the mel store / output
+ * 16-byte aligned (the mel rows move as 16-byte words).  The device tables must hold what the
+ * host copies hold.                                                                          */
+int fs2_batch_gather(const int32_t* idx, const int32_t* idx_host, int64_t batch, int64_t n_utt,
+                     const int32_t* src_len_host, const int32_t* mel_len_host,
+                     const int32_t* src_len, const int32_t* mel_len, const int64_t* src_off,
+                     const int64_t* mel_off, const int64_t* speaker, const int64_t* text,
+                     const int64_t* dur, const int64_t* accent, const float* mel,
+                     const float* pitch, const void* energy, const float* meta, int64_t n_mels,
+                     int64_t meta_dim, int64_t energy_bytes, int64_t pitch_frame,
+                     int64_t energy_frame, int64_t max_src_len, int64_t max_mel_len,
+                     int64_t* o_text, int64_t* o_dur, int64_t* o_accent, float* o_mel,
+                     float* o_pitch, void* o_energy, int64_t* o_src_len, int64_t* o_mel_len,
+                     int64_t* o_speaker, float* o_meta, void* stream);
+/* Validation sums kept on the device (evaluate.py:68-72), one call per batch:
+ * sums[i] (double[6]) += (double)losses[i] * batch, esum[0] (float) += eloss[0] * batch (the
+ * product rounded to fp32 first, as the reference's tensor expression); eloss nullable.      */
+int fs2_eval_accum(double* sums, float* esum, const float* losses, const float* eloss,
+                   int64_t batch, void* stream);
 /* ---- Exact t-SNE of speaker embeddings (train_speech_embedder.py:311-385; the semantics of
  * scikit-learn's TSNE(2, init='pca', method='exact'), Euclidean metric).  fp32 storage; limits
  * for every entry: n <= 4096 points, dim <= 1024, 2 output components.  n = 0 launches nothing.

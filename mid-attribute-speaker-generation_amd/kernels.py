@@ -1293,6 +1293,71 @@ def epoch_stats_add(totals, loss=None, da_loss=None, logit=None, y=None, correct
                             ptr(correct), stream())
 
 
+def _host_i32(a, n, what):
+    import numpy as np
+    if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous and
+            a.size == n):
+        raise RuntimeError(f"batch_gather: {what} must be a contiguous host int32[{n}] array")
+    return a.ctypes.data
+
+
+def batch_gather(st, idx, idx_host, max_src_len, max_mel_len, accents=True, out=None):
+    """The padded training batch of the utterances ``idx`` (device int32[B]; ``idx_host`` its host
+    copy, which the entry point validates against the store's host tables before it launches) of
+    a device-resident corpus ``st`` (``corpus_store.CorpusStore``: flat ``text``, ``dur``,
+    ``accent``, ``mel``, ``pitch``, ``energy``, ``meta`` stores, the device tables
+    ``d_src_len``, ``d_mel_len``, ``d_src_off``, ``d_mel_off``, ``d_speaker`` and the host tables
+    ``src_len``, ``mel_len``) in one launch (fs2_batch_gather).  Returns ``(speakers, texts,
+    src_lens, mels, mel_lens, pitches, energies, durations, speaker_meta, accents or None)`` with
+    ``to_device``'s dtypes; ``out``: such a tuple of the same shapes to write into."""
+    B, n = idx.numel(), len(st)
+    Ts, Tm, C, Md = int(max_src_len), int(max_mel_len), st.n_mels, st.meta_dim
+    pf, ef = st.levels
+    dev = st.mel.device
+    _dev(idx, st.text, st.dur, st.accent, st.mel, st.pitch, st.energy, st.meta, st.d_src_len,
+         st.d_mel_len, st.d_src_off, st.d_mel_off, st.d_speaker)
+    if idx.dtype != torch.int32:
+        raise RuntimeError("batch_gather: idx must be device int32")
+    i64, f32 = torch.int64, torch.float32
+    spec = (((B,), i64), ((B, Ts), i64), ((B,), i64), ((B, Tm, C), f32), ((B,), i64),
+            ((B, Tm if pf else Ts), f32), ((B, Tm if ef else Ts), st.energy.dtype),
+            ((B, Ts), i64), ((B, Md), f32), ((B, Ts), i64))
+    if out is None:
+        out = [torch.empty(s, dtype=d, device=dev) for s, d in spec]
+        if not accents:
+            out[9] = None
+    else:
+        out = list(out)
+        if len(out) != 10 or (out[9] is None) == bool(accents):
+            raise RuntimeError("batch_gather: out must be a tuple this function returned")
+        for t, (s, d) in zip(out, spec):
+            if t is not None and (tuple(t.shape) != s or t.dtype != d):
+                raise RuntimeError(f"batch_gather: out tensor {tuple(t.shape)} {t.dtype}, "
+                                   f"expected {s} {d}")
+        _dev(*out)
+    spk, texts, sl, mels, ml, pit, ene, dur, meta, acc = out
+    lib.fs2_batch_gather(
+        ptr(idx), _host_i32(idx_host, B, "idx_host"), B, n,
+        _host_i32(st.src_len, n, "src_len"), _host_i32(st.mel_len, n, "mel_len"),
+        ptr(st.d_src_len), ptr(st.d_mel_len), ptr(st.d_src_off), ptr(st.d_mel_off),
+        ptr(st.d_speaker), ptr(st.text), ptr(st.dur), ptr(st.accent), ptr(st.mel), ptr(st.pitch),
+        ptr(st.energy), ptr(st.meta), C, Md, st.energy.element_size(), int(pf), int(ef), Ts, Tm,
+        ptr(texts), ptr(dur), ptr(acc), ptr(mels), ptr(pit), ptr(ene), ptr(sl), ptr(ml), ptr(spk),
+        ptr(meta), stream())
+    return tuple(out)
+
+
+def eval_accum(sums, esum, losses, eloss, batch):
+    """sums (device double[6]) += losses (device float[6]) * batch; esum (device float[1]) +=
+    eloss * batch: the validation sums of evaluate.py:68-72 without a host read
+    (fs2_eval_accum)."""
+    _dev(sums, esum, losses, eloss)
+    if (sums.dtype, esum.dtype, losses.dtype) != (torch.float64, torch.float32, torch.float32) \
+            or sums.numel() != 6 or losses.numel() != 6:
+        raise RuntimeError("eval_accum: sums f64[6], esum f32[1], losses f32[6]")
+    lib.fs2_eval_accum(ptr(sums), ptr(esum), ptr(losses), ptr(eloss), int(batch), stream())
+
+
 def sched_step(steps, hyper, init_lr, n_warmup, anneal_steps, anneal_rate, beta1, beta2,
                advance_lr=True):
     """Device-side LR schedule + Adam bias corrections for one step (fs2_sched_step)."""
