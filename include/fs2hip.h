@@ -1251,6 +1251,48 @@ int fs2_debug_snap(void* buf, int64_t cap);
 int fs2_debug_coherence(void* x, int64_t n, int rounds, int blocks, void* bad, void* stream);
 int64_t fs2_debug_snap_used(void);
 
+/* ---------------------------------------------------------------- objective synthesis metrics
+ * Not in the reference (it judges synthesis by ear, through TensorBoard samples): MFCCs of this
+ * project's natural-log mels, dynamic time warping with its path, and per-pair records along
+ * the path (csrc/metrics.hip).
+ *
+ * fs2_mfcc: coefficients 1..n_coef of the orthonormal DCT-II over the mel axis (c0 dropped).
+ * logmel is (B, n_mels, F) (rows = 0, MelFrontEnd's layout) or (B * F, n_mels) (rows = 1, the
+ * model's row layout); n_frames (device int64[B], nullable = F everywhere) is not read back;
+ * dct is the host-built table (n_mels, n_coef), dct[m * n_coef + k - 1] =
+ * sqrt(2 / n_mels) cos(pi (2 m + 1) k / (2 n_mels)) formed in fp64 and rounded once;
+ * out (B, F, n_coef), rows at and past n_frames zero.  1 <= n_coef < n_mels <= 128.
+ *
+ * fs2_dtw: per pair p, a[p] (T1max, K) and b[p] (T2max, K) fp32 with device lengths la[p] in
+ * 1..T1max, lb[p] in 1..T2max (int64; a length outside its range is clamped into it, rows at
+ * and past a length are never read).  fp64: c(i, j) = sqrt(sum_k (a_ik - b_jk)^2),
+ * D(0, 0) = c(0, 0), D(i, j) = c(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)) with the first
+ * minimum in that order taken and a predecessor outside the matrix +inf: one add per cell.
+ * cost[p] = D(la-1, lb-1); path (B, T1max + T2max - 1, 2) int32 runs from (0, 0) to
+ * (la-1, lb-1), path_len[p] entries (the rest is left as it was).  One workgroup per pair sweeps
+ * the anti-diagonals with the last three in LDS; the workspace holds one step byte per cell,
+ * the reversed path and a feature-major copy of the pair's live rows, never the matrix
+ * (fs2_dtw_ws_bytes); the path is traced in the same launch.  T1max, T2max <= 2048, K >= 1.
+ *
+ * fs2_path_metrics: rec (B, FS2_METRIC_FIELDS) fp64 per pair = [path_len, mcd_db =
+ * (10 / ln 10) sqrt(2) cost / path_len, frames_a, frames_b, n_vv, f0_sq_cents, n_vuv,
+ * len_err = (frames_a - frames_b) / frames_b].  With fa (B, T1max) and fb (B, T2max) fp32
+ * contours (0 = unvoiced; both or neither): n_vv = path pairs voiced in both, f0_sq_cents =
+ * sum over them of (1200 log2(fa / fb))^2, n_vuv = path pairs whose voicing differs; without
+ * them the three fields are 0.  Sums in fp64 in a fixed order.                            */
+#define FS2_METRIC_FIELDS 8
+#define FS2_DTW_MAX_LEN 2048
+#define FS2_MFCC_MAX_MELS 128
+int fs2_mfcc(const float* logmel, const int64_t* n_frames, int64_t batch, int64_t n_mels,
+             int64_t frames, int rows, const float* dct, int64_t n_coef, float* out, void* stream);
+int64_t fs2_dtw_ws_bytes(int64_t batch, int64_t t1_max, int64_t t2_max, int64_t k);
+int fs2_dtw(const float* a, const float* b, const int64_t* la, const int64_t* lb, int64_t batch,
+            int64_t t1_max, int64_t t2_max, int64_t k, double* cost, int* path, int* path_len,
+            void* ws, int64_t ws_bytes, void* stream);
+int fs2_path_metrics(const double* cost, const int* path, const int* path_len, const int64_t* la,
+                     const int64_t* lb, int64_t batch, int64_t t1_max, int64_t t2_max,
+                     const float* fa, const float* fb, double* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1468,3 +1468,92 @@ def gmm_bary_mix(pi, mu, sd, rate64, bm, bs):
                          ptr(n_used), ptr(used), ptr(pi_o), ptr(mu_o), ptr(sd_o), ptr(w), n,
                          stream())
     return n_used, used, pi_o, mu_o, sd_o
+
+
+# ------------------------------------------------------------------ objective synthesis metrics
+METRIC_FIELDS = 8    # FS2_METRIC_FIELDS
+DTW_MAX_LEN = 2048   # FS2_DTW_MAX_LEN
+
+
+def _lens_i64(name, lens, batch):
+    _dev(lens)
+    if lens.dtype != torch.int64 or lens.numel() != batch:
+        raise RuntimeError(f"{name}: lengths are device int64 ({batch})")
+
+
+def mfcc(logmel, n_frames, dct, rows=False):
+    """Coefficients 1..K of the orthonormal DCT-II over the mel axis (fs2_mfcc): logmel
+    (B, n_mels, F) f32, or with ``rows`` the model's row layout (B, F, n_mels) / (B * F, n_mels);
+    n_frames device int64 (B) (None: every frame; needed for the 2-D row layout, whose batch
+    it gives); dct (n_mels, K) f32, ``metrics.dct_table`` -> (B, F, K), zeros past n_frames."""
+    _dev(logmel, n_frames, dct)
+    if logmel.dtype != torch.float32 or dct.dtype != torch.float32 or dct.dim() != 2:
+        raise RuntimeError("mfcc: logmel and the DCT table are f32")
+    n_mels, n_coef = dct.shape
+    if rows:
+        if logmel.dim() == 3:
+            B, F = logmel.shape[:2]
+        elif logmel.dim() == 2 and n_frames is not None and logmel.shape[0] % n_frames.numel() == 0:
+            B = n_frames.numel()
+            F = logmel.shape[0] // B
+        else:
+            raise RuntimeError("mfcc: the row layout is (B, F, n_mels), or (B * F, n_mels) with "
+                               "n_frames (B)")
+        ok = logmel.shape[-1] == n_mels
+    else:
+        ok = logmel.dim() == 3 and logmel.shape[1] == n_mels
+        B, F = (logmel.shape[0], logmel.shape[2]) if ok else (0, 0)
+    if not ok:
+        raise RuntimeError(f"mfcc: logmel {tuple(logmel.shape)} does not have the table's "
+                           f"{n_mels} mel channels")
+    if n_frames is not None:
+        _lens_i64("mfcc", n_frames, B)
+    out = torch.empty((B, F, n_coef), dtype=torch.float32, device=logmel.device)
+    lib.fs2_mfcc(ptr(logmel), ptr(n_frames), B, n_mels, F, int(bool(rows)), ptr(dct), n_coef,
+                 ptr(out), stream())
+    return out
+
+
+def dtw(a, b, la, lb):
+    """Batched dynamic time warping with its path (fs2_dtw): a (B, T1max, K), b (B, T2max, K) f32,
+    la / lb device int64 (B) -> ``(cost (B) f64, path (B, T1max + T2max - 1, 2) int32,
+    path_len (B) int32)``; entries of ``path`` past ``path_len`` are unwritten."""
+    _dev(a, b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 3 or b.dim() != 3 or \
+            a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
+        raise RuntimeError("dtw: a (B, T1max, K) and b (B, T2max, K) are f32")
+    B, T1, Kf = a.shape
+    T2, dev = b.shape[1], a.device
+    _lens_i64("dtw", la, B)
+    _lens_i64("dtw", lb, B)
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    path = torch.empty((B, max(T1 + T2 - 1, 0), 2), dtype=torch.int32, device=dev)
+    path_len = torch.empty(B, dtype=torch.int32, device=dev)
+    nb = lib.fs2_dtw_ws_bytes(B, T1, T2, Kf)
+    wk = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    lib.fs2_dtw(ptr(a), ptr(b), ptr(la), ptr(lb), B, T1, T2, Kf, ptr(cost), ptr(path),
+                ptr(path_len), ptr(wk), nb, stream())
+    return cost, path, path_len
+
+
+def path_metrics(cost, path, path_len, la, lb, t1_max, t2_max, fa=None, fb=None):
+    """The per-pair records along DTW paths (fs2_path_metrics) -> (B, METRIC_FIELDS) f64:
+    path_len, mcd_db, frames_a, frames_b, n_vv, f0_sq_cents, n_vuv, len_err; fa (B, T1max) and
+    fb (B, T2max) f32 F0 contours (0 = unvoiced), both or neither."""
+    _dev(cost, path, path_len, fa, fb)
+    B, T1, T2 = cost.numel(), int(t1_max), int(t2_max)
+    if cost.dtype != torch.float64 or path.dtype != torch.int32 or path_len.dtype != torch.int32 \
+            or tuple(path.shape) != (B, T1 + T2 - 1, 2) or path_len.numel() != B:
+        raise RuntimeError("path_metrics: cost f64 (B), path int32 (B, T1max + T2max - 1, 2), "
+                           "path_len int32 (B)")
+    _lens_i64("path_metrics", la, B)
+    _lens_i64("path_metrics", lb, B)
+    if (fa is None) != (fb is None):
+        raise RuntimeError("path_metrics: the F0 contours come as a pair or not at all")
+    if fa is not None and (fa.dtype != torch.float32 or fb.dtype != torch.float32 or
+                           tuple(fa.shape) != (B, T1) or tuple(fb.shape) != (B, T2)):
+        raise RuntimeError(f"path_metrics: F0 contours are f32 ({B}, {T1}) and ({B}, {T2})")
+    rec = torch.empty((B, METRIC_FIELDS), dtype=torch.float64, device=cost.device)
+    lib.fs2_path_metrics(ptr(cost), ptr(path), ptr(path_len), ptr(la), ptr(lb), B, T1, T2, ptr(fa),
+                         ptr(fb), ptr(rec), stream())
+    return rec
