@@ -476,6 +476,68 @@ int fs2_griffin_lim_step(const float* wav_in, const float* mag, const int64_t* n
 int fs2_f0_yin(const float* wav, const int64_t* lens, int64_t batch, int64_t samples, int64_t hop,
                double sr, double f0_floor, double f0_ceil, double threshold, float* f0, float* dip,
                int64_t* n_frames, void* stream);
+/* The F0 contour by pYIN (Mauch & Dixon, ICASSP 2014): every threshold of a prior distribution
+ * votes for the pick fs2_f0_yin would make at it, and a Viterbi pass over (pitch bin, voiced /
+ * unvoiced) states picks the track.  Opt-in beside fs2_f0_yin; nothing is compared with librosa's
+ * or the authors' code.  wav, lens, the frames, s[j], d(tau), d'(tau), tau_min, tau_max, W = 512,
+ * the descent, the parabola and the [f0_floor, f0_ceil] test are exactly those of fs2_f0_yin
+ * (the same fp32 operations in the same order, no fused multiply-add).
+ *
+ * Candidates (fs2_f0_pyin_candidates).  Thresholds theta_i = float32(i / 100), i = 1..100, with
+ * prior (100) fp64 holding w_i = I(theta_i) - I(theta_(i-1)), I the Beta(2, 18) CDF
+ * 1 - (1 - x)^19 - 19 x (1 - x)^18 (audio.pyin_tables).  Threshold i picks the first tau in
+ * [tau_min, tau_max] with d'(tau) < theta_i, advanced while d'(tau + 1) < d'(tau), with mass w_i;
+ * if no tau qualifies, the first argmin of d' over the range with mass w_i * 0.01 (one fp64
+ * product) -- and no mass at all unless d' there is below 1: where a frame has no energy d' is 1
+ * by convention, and such a frame votes for nothing.  The pick is refined by the parabola; an f0 outside [f0_floor, f0_ceil] drops its
+ * mass (it counts as unvoiced), otherwise its bin is
+ *   b = clamp(rint(60 log2((double)f0 / (double)(float)f0_floor)), 0, n_bins - 1)   (fp64),
+ * 60 = 12 semitones of 5 bins; the caller passes n_bins = floor(60 log2(f0_ceil / f0_floor)) + 1
+ * (210 for 71..800 Hz), 1 <= n_bins <= 1024.  Per live frame:
+ *   mass[b]    = the fp64 sum of the masses of the thresholds picking bin b, i ascending
+ *   cand_f0[b] = the f0 of the lowest such i (fp32), 0 for a bin nobody picked
+ *   voiced     = min(sum_b mass[b], 1), one fp64 accumulator, b ascending
+ *   unvoiced   = (float)(1 - voiced) (nullable): small means strongly periodic, as dip
+ * mass (batch, F_max, n_bins) fp64, cand_f0 (batch, F_max, n_bins) fp32, voiced (batch, F_max)
+ * fp64, unvoiced (batch, F_max) fp32, all zeros at k >= n_frames; n_frames (batch) int64.
+ *
+ * Viterbi (fs2_f0_pyin_viterbi) over the states s = b (voiced) and n_bins + b (unvoiced), in
+ * the probability domain with no logarithms.  mass (batch, frames, n_bins) and voiced (batch,
+ * frames) fp64 as above; n_frames (batch) device int64, nullable = frames, read clamped into
+ * [0, frames]; tri (reach + 1) fp64 with tri(d) = (R + 1 - d) / (R + 1)^2 for the reach
+ * R = round(35.92 * 60 * hop / sr) (25 at hop 256 and 22 050 Hz), 0 <= R <= 1023.
+ *   obs_k(b)          = mass_k[b] + 1e-9;  obs_k(n_bins + b) = (1 - voiced_k) / n_bins + 1e-9
+ *   P((b', v')|(b, v)) = tri(|b' - b|) * (0.99 if v' = v else 0.01) for |b' - b| <= R, else 0;
+ *                       what leaves the bin range at the edges is not redistributed
+ *   delta_0           = obs_0 / (2 n_bins), then divided by its maximum
+ *   delta_k(s')       = (max_s delta_(k-1)(s) * P(s'|s)) * obs_k(s'), then the frame is divided
+ *                       by its maximum
+ * every operation one IEEE fp64 multiply, divide or compare (no fused multiply-add), so numpy
+ * gives the same bits.  Ties go to the lowest predecessor and the lowest final state (numpy's
+ * argmax); the path is traced back from frame n_frames - 1.  path (batch, frames) int32
+ * receives the states, -1 at k >= n_frames.  With f0 (batch, frames) fp32 (nullable; it needs
+ * cand_f0 and centres (n_bins) fp32 = float32(f0_floor 2^(b / 60))): 0 for an unvoiced state,
+ * cand_f0_k[b] for a voiced one where that is non-zero, else centres[b]; 0 at k >= n_frames.
+ * ws (fs2_f0_pyin_viterbi_ws_bytes) holds int16 back-pointers (batch, frames, 2 n_bins).
+ *
+ * fs2_f0_pyin runs both stages on the stream: f0 and unvoiced (batch, F_max) fp32, n_frames
+ * (batch) int64, states (batch, F_max) int32 (nullable), ws of fs2_f0_pyin_ws_bytes.  A row's
+ * result never depends on its place in the batch.  batch = 0 launches nothing; bad arguments are
+ * FS2_ERR_ARG before any launch; lens is never read back.                                    */
+int fs2_f0_pyin_candidates(const float* wav, const int64_t* lens, int64_t batch, int64_t samples,
+                           int64_t hop, double sr, double f0_floor, double f0_ceil,
+                           const double* prior, int64_t n_bins, double* mass, float* cand_f0,
+                           double* voiced, float* unvoiced, int64_t* n_frames, void* stream);
+int64_t fs2_f0_pyin_viterbi_ws_bytes(int64_t batch, int64_t frames, int64_t n_bins);
+int fs2_f0_pyin_viterbi(const double* mass, const double* voiced, const int64_t* n_frames,
+                        int64_t batch, int64_t frames, int64_t n_bins, const double* tri,
+                        int64_t reach, const float* cand_f0, const float* centres, int* path,
+                        float* f0, void* ws, int64_t ws_bytes, void* stream);
+int64_t fs2_f0_pyin_ws_bytes(int64_t batch, int64_t samples, int64_t hop, int64_t n_bins);
+int fs2_f0_pyin(const float* wav, const int64_t* lens, int64_t batch, int64_t samples, int64_t hop,
+                double sr, double f0_floor, double f0_ceil, const double* prior, const double* tri,
+                int64_t reach, const float* centres, int64_t n_bins, float* f0, float* unvoiced,
+                int64_t* n_frames, int* states, void* ws, int64_t ws_bytes, void* stream);
 /* Rational polyphase FIR resampling of a ragged batch, where preprocessor/preprocessor.py:186
  * calls librosa.load(sr=22050) (no parity with resampy's interpolated filter table is claimed).
  * wav (batch, samples) fp32, lens (device int64, nullable = samples; read clamped into

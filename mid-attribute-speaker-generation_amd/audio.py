@@ -18,10 +18,12 @@ construction (fp64, rounded to fp32); the arithmetic on samples runs in the kern
 common/layers.py:125-141): mel inversion, inverse STFT and the Griffin-Lim loop on the same
 tables, and a ``forward_rows`` that stands in for the vocoder where no checkpoint exists.
 
-Beside it: ``PitchExtractor`` (YIN F0 on the same frames), ``SilenceSplitter``
+Beside it: ``PitchExtractor`` (YIN or pYIN F0 on the same frames), ``SilenceSplitter``
 (``librosa.effects.split``, the speaker encoder's data_preprocess.py:46) and ``Resampler``
 (``librosa.load``'s rate conversion).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -309,16 +311,54 @@ class GriffinLim:
         return wav, (wav * float(max_wav_value)).to(torch.int32).to(torch.int16) if pcm else None
 
 
+PYIN_THRESHOLDS, PYIN_BINS_PER_SEMITONE, PYIN_MAX_BINS = 100, 5, 1024
+
+
+def pyin_tables(hop, sr, f0_floor=71.0, f0_ceil=800.0):
+    """The host tables of ``fs2_f0_pyin`` as numpy arrays ``(prior f64 (100), tri f64 (R + 1),
+    centres f32 (n_bins))``, Python floats throughout so that any host computes the same bits:
+
+      prior[i - 1] = I(theta_i) - I(theta_(i-1)), theta_i = float32(i / 100), theta_0 = 0, I the
+                     Beta(2, 18) CDF 1 - (1 - x)^19 - 19 x (1 - x)^18
+      tri[d]       = (R + 1 - d) / (R + 1)^2, R = round(35.92 * 60 * hop / sr): the widest jump
+                     between two frames, 35.92 octaves per second
+      centres[b]   = float32(f0_floor 2^(b / 60)), n_bins = floor(60 log2(f0_ceil / f0_floor)) + 1
+    """
+    step = 12 * PYIN_BINS_PER_SEMITONE
+
+    def cdf(x):
+        return 1.0 - (1.0 - x) ** 19 - 19.0 * x * (1.0 - x) ** 18
+
+    th = [0.0] + [float(np.float32(i / 100.0)) for i in range(1, PYIN_THRESHOLDS + 1)]
+    prior = np.array([cdf(th[i]) - cdf(th[i - 1]) for i in range(1, PYIN_THRESHOLDS + 1)])
+    R = int(round(35.92 * step * hop / sr))
+    tri = np.array([(R + 1 - d) / float((R + 1) ** 2) for d in range(R + 1)])
+    n_bins = int(math.floor(step * math.log2(f0_ceil / f0_floor))) + 1
+    centres = np.array([f0_floor * 2.0 ** (b / float(step)) for b in range(n_bins)]).astype(np.float32)
+    return prior, tri, centres
+
+
 class PitchExtractor:
     """The F0 contour on the frames of ``MelFrontEnd`` (centres ``k * hop``, ``1 + len // hop`` of
     them: the count ``pw.dio`` returns for ``frame_period = hop / sr``), by YIN
     (``fs2_f0_yin``).  The reference (preprocessor.py:196-201) calls pyworld's DIO + StoneMask;
     this is another estimator and its values are not DIO's.  ``dip`` is the normalised
     difference function at the chosen lag (its minimum over the lag range for an unvoiced
-    frame): small means strongly periodic."""
+    frame): small means strongly periodic.
+
+    ``method="pyin"`` is pYIN (``fs2_f0_pyin``; Mauch & Dixon 2014): every threshold of a
+    Beta(2, 18) prior votes for YIN's pick at it and a Viterbi pass over (pitch bin, voiced /
+    unvoiced) states picks the track, which keeps the voicing decision steady in noise.
+    ``threshold`` is ignored by it, and the second result is ``unvoiced``, 1 - the voiced prior
+    mass of the frame, in ``dip``'s place and sense."""
+
+    METHODS = ("yin", "pyin")
 
     def __init__(self, preprocess_config=None, device="cuda", f0_floor=71.0, f0_ceil=800.0,
-                 threshold=0.15):
+                 threshold=0.15, method="yin"):
+        if method not in self.METHODS:
+            raise ValueError(f"method {method!r}: one of {list(self.METHODS)}")
+        self.method = method
         pp = preprocess_config if preprocess_config is not None else load_configs()[0]
         self.hop = int(pp["stft"]["hop_length"])
         self.sr = int(pp["audio"]["sampling_rate"])
@@ -331,15 +371,25 @@ class PitchExtractor:
             raise ValueError(f"f0_floor {f0_floor} at {self.sr} Hz needs {int(self.sr // self.f0_floor)} "
                              "lags: the kernel is built for at most 512")
         self.device = torch.device(device)
+        self.tables = None
+        if method == "pyin":
+            prior, tri, centres = pyin_tables(self.hop, self.sr, self.f0_floor, self.f0_ceil)
+            if len(centres) > PYIN_MAX_BINS:
+                raise ValueError(f"f0 range {f0_floor}..{f0_ceil}: {len(centres)} pitch bins, the "
+                                 f"kernel is built for at most {PYIN_MAX_BINS}")
+            if len(tri) > 1024:
+                raise ValueError(f"hop_length {self.hop} at {self.sr} Hz: a reach of {len(tri) - 1} "
+                                 "bins per frame, the kernel is built for at most 1023")
+            self.tables = tuple(torch.from_numpy(t).to(self.device) for t in (prior, tri, centres))
 
     def n_frames(self, length):
         return frame_count(length, self.hop)
 
     def __call__(self, wav, lens=None):
         """wav (B, S) or (S,) on the device -> ``(f0 (B, F), dip (B, F), n_frames (B) int64)``,
-        F = 1 + S // hop, zeros past ``n_frames`` (without the batch axis for a 1-D wav).
-        ``lens`` as in ``MelFrontEnd.__call__``: None, a host list (checked) or a device int64
-        tensor (not read back)."""
+        F = 1 + S // hop, zeros past ``n_frames`` (without the batch axis for a 1-D wav); with
+        ``method="pyin"`` the second is ``unvoiced``.  ``lens`` as in ``MelFrontEnd.__call__``:
+        None, a host list (checked) or a device int64 tensor (not read back)."""
         single = wav.dim() == 1
         w = (wav[None] if single else wav).contiguous()
         if w.dtype != torch.float32:
@@ -354,7 +404,10 @@ class PitchExtractor:
                     raise ValueError(f"length {n}: 0..{S} samples")
             lens = torch.from_numpy(np.asarray(lens, np.int64)).pin_memory().to(w.device,
                                                                                  non_blocking=True)
-        out = K.f0_yin(w, lens, self.hop, self.sr, self.f0_floor, self.f0_ceil, self.threshold)
+        if self.method == "pyin":
+            out = K.f0_pyin(w, lens, self.hop, self.sr, self.f0_floor, self.f0_ceil, *self.tables)
+        else:
+            out = K.f0_yin(w, lens, self.hop, self.sr, self.f0_floor, self.f0_ceil, self.threshold)
         return tuple(o[0] for o in out) if single else out
 
 

@@ -4,7 +4,8 @@
 // interpolation over unvoiced frames, the phoneme-level means, the outlier filter with the
 // running moments, and the normalisation with the running extrema.
 //
-// fs2_f0_yin.  A block of 4 waves owns PT_FPB = 8 consecutive frames of one utterance and stages
+// fs2_f0_yin (the d' stage and the lag refinement live in yin_core.hpp, which pyin.hip shares).
+// A block of 4 waves owns PT_FPB = 8 consecutive frames of one utterance and stages
 // their sample span ((PT_FPB - 1) hop + 512 + 64 TL + 8 floats, zeros outside [0, len)) into LDS
 // once; each wave then owns two of the frames.  A lane keeps TL consecutive lags
 // tau = TL lane + 1 + r in registers (TL the smallest odd number with 64 TL >= tau_max: 5 for
@@ -26,16 +27,13 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "yin_core.hpp"  // the d' stage and the lag refinement, shared with pyin.hip
 
 #pragma clang fp contract(off)
 
 namespace fs2 {
 
-constexpr int PT_W = 512, PT_FPB = 8, PT_WAVES = 4, PT_FPW = PT_FPB / PT_WAVES, PT_JB = 8;
-constexpr int PT_TAU_CAP = 512;
-constexpr int PT_DLEN = PT_TAU_CAP + 8;  // d(0 .. tau_max) of one frame
-constexpr int PT_ROW_CAP = 15360;        // frames of a row the small kernels hold in LDS
+constexpr int PT_ROW_CAP = 15360;  // frames of a row the small kernels hold in LDS
 
 struct F0Yin {
   const float* wav;
@@ -51,8 +49,6 @@ struct F0Yin {
   int64_t* n_frames;
 };
 
-FS2_DEV int pt_span_floats(int hop, int tl) { return (PT_FPB - 1) * hop + PT_W + 64 * tl + PT_JB; }
-
 template <int TL>
 __global__ __launch_bounds__(64 * PT_WAVES) void f0_yin_kernel(F0Yin a) {
   extern __shared__ float smem[];
@@ -61,9 +57,7 @@ __global__ __launch_bounds__(64 * PT_WAVES) void f0_yin_kernel(F0Yin a) {
   const int64_t b = blockIdx.x / a.chunks;
   const int fr0 = (int)(blockIdx.x - b * a.chunks) * PT_FPB;
   const int64_t F_max = a.F_max;
-  int64_t len64 = a.lens ? a.lens[b] : a.S;
-  len64 = len64 < 0 ? 0 : len64 > a.S ? a.S : len64;
-  const int len = (int)len64;
+  const int len = pt_row_len(a.lens, b, a.S);
   const int nf = 1 + len / hop;
   if (fr0 == 0 && tid == 0) a.n_frames[b] = nf;
   const int fcnt = (int)(F_max - fr0 < PT_FPB ? F_max - fr0 : PT_FPB);
@@ -73,76 +67,7 @@ __global__ __launch_bounds__(64 * PT_WAVES) void f0_yin_kernel(F0Yin a) {
     if (tid < fcnt) f0_b[fr0 + tid] = 0.f, dip_b[fr0 + tid] = 0.f;
     return;
   }
-
-  // region A: the span, later the running sums of the block's frames; region D: d, then d'
-  const int span_n = pt_span_floats(hop, TL);
-  const int a_n = span_n > PT_FPB * PT_DLEN ? span_n : PT_FPB * PT_DLEN;
-  float* span = smem;
-  float* dall = smem + ((a_n + 3) & ~3);
-  {
-    const float* row = a.wav + b * a.S;
-    const int p0 = fr0 * hop - (PT_W + tmax) / 2;
-    for (int i = tid; i < span_n; i += 64 * PT_WAVES) {
-      const int p = p0 + i;
-      span[i] = p >= 0 && p < len ? row[p] : 0.f;
-    }
-  }
-  __syncthreads();
-
-#pragma unroll
-  for (int q = 0; q < PT_FPW; ++q) {
-    const int jf = wave * PT_FPW + q;  // frame within the block
-    const float* seg = span + jf * hop;
-    const float* mine = seg + TL * lane + 1;
-    float acc[TL];
-#pragma unroll
-    for (int r = 0; r < TL; ++r) acc[r] = 0.f;
-    for (int j0 = 0; j0 < PT_W; j0 += PT_JB) {
-      float sj[PT_JB], win[TL + PT_JB - 1];
-#pragma unroll
-      for (int jj = 0; jj < PT_JB; ++jj) sj[jj] = seg[j0 + jj];
-#pragma unroll
-      for (int k = 0; k < TL + PT_JB - 1; ++k) win[k] = mine[j0 + k];
-#pragma unroll
-      for (int jj = 0; jj < PT_JB; ++jj)
-#pragma unroll
-        for (int r = 0; r < TL; ++r) {
-          const float df = sj[jj] - win[jj + r];
-          const float sq = df * df;
-          acc[r] = acc[r] + sq;
-        }
-    }
-    float* d = dall + jf * PT_DLEN;
-#pragma unroll
-    for (int r = 0; r < TL; ++r) {
-      const int tau = TL * lane + 1 + r;
-      if (tau <= tmax) d[tau] = acc[r];
-    }
-  }
-  __syncthreads();  // the span is dead from here on
-
-  float* csall = smem;
-  if (lane < PT_FPW) {  // the running sum, sequential as the definition has it
-    const float* d = dall + (wave * PT_FPW + lane) * PT_DLEN;
-    float* cs = csall + (wave * PT_FPW + lane) * PT_DLEN;
-    float run = 0.f;
-    for (int tau = 1; tau <= tmax; ++tau) {
-      run = run + d[tau];
-      cs[tau] = run;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < PT_FPW; ++q) {
-    float* d = dall + (wave * PT_FPW + q) * PT_DLEN;
-    const float* cs = csall + (wave * PT_FPW + q) * PT_DLEN;
-    for (int tau = 1 + lane; tau <= tmax; tau += 64) {
-      const float c = cs[tau];
-      d[tau] = c != 0.f ? (d[tau] * (float)tau) / c : 1.f;
-    }
-    if (lane == 0) d[0] = 1.f;
-  }
-  __syncthreads();
+  const float* dall = pt_dprime<TL>(smem, a.wav + b * a.S, len, fr0, hop, tmax);
 
 #pragma unroll
   for (int q = 0; q < PT_FPW; ++q) {
@@ -162,18 +87,8 @@ __global__ __launch_bounds__(64 * PT_WAVES) void f0_yin_kernel(F0Yin a) {
       dp = -wave_max(-m);
     } else {
       int tau = first;
-      while (tau + 1 <= tmax && d[tau + 1] < d[tau]) ++tau;
+      f = pt_refine(d, tau, tmax, a.sr);
       dp = d[tau];
-      float off = 0.f;
-      if (tau < tmax) {
-        const float ya = d[tau - 1], yb = d[tau], yc = d[tau + 1];
-        const float den = (ya - 2.f * yb) + yc;
-        if (den > 0.f) {
-          off = (0.5f * (ya - yc)) / den;
-          off = off < -1.f ? -1.f : off > 1.f ? 1.f : off;
-        }
-      }
-      f = a.sr / ((float)tau + off);
       if (f < a.lo || f > a.hi) f = 0.f;
     }
     if (lane == 0 && fr < F_max) {
@@ -428,13 +343,10 @@ int fs2_f0_yin(const float* wav, const int64_t* lens, int64_t batch, int64_t sam
   FS2_CHECK_ARG(batch * chunks < (1ll << 31), "fs2_f0_yin: batch %lld x %lld frames too large",
                 (long long)batch, (long long)F_max);
   const int tmax = (int)tmax_d, tmin = (int)tmin_d;
-  int tl = (tmax + 63) / 64;
-  tl += 1 - (tl & 1);  // odd: lanes TL dwords apart fall into different LDS banks
+  const int tl = pt_lags_per_lane(tmax);
   F0Yin a{wav, lens, samples, (int)hop, F_max, (int)chunks, tmin, tmax, (float)sr, (float)f0_floor,
           (float)f0_ceil, (float)threshold, f0, dip, n_frames};
-  const int span_n = (PT_FPB - 1) * (int)hop + PT_W + 64 * tl + PT_JB;
-  const int a_n = span_n > PT_FPB * PT_DLEN ? span_n : PT_FPB * PT_DLEN;
-  const size_t lds = sizeof(float) * (size_t)(((a_n + 3) & ~3) + PT_FPB * PT_DLEN);
+  const size_t lds = pt_lds_bytes((int)hop, tl);
   const dim3 grid((unsigned)(batch * chunks));
   hipStream_t st = as_stream(stream);
   switch (tl) {

@@ -1090,6 +1090,109 @@ def f0_yin(wav, lens, hop, sr, f0_floor=71.0, f0_ceil=800.0, threshold=0.15, out
     return f0, dip, nf
 
 
+def _pyin_table(name, what, t, dtype, numel, dev):
+    _dev(t)
+    if t.dtype != dtype or t.dim() != 1 or t.numel() != numel or t.device != dev:
+        raise RuntimeError(f"{name}: {what} is {str(dtype).split('.')[-1]} ({numel}) on {dev}")
+
+
+def _pyin_hop(name, hop):
+    hop = int(hop)
+    if not 1 <= hop <= 1024:
+        raise RuntimeError(f"{name}: hop {hop} (1..1024)")
+    return hop
+
+
+def f0_pyin_candidates(wav, lens, hop, sr, f0_floor, f0_ceil, prior, n_bins):
+    """The first stage of pYIN (fs2_f0_pyin_candidates): wav (B, S) f32, lens device int64 (B) or
+    None, ``prior`` device f64 (100) -> ``(mass (B, F, n_bins) f64, cand_f0 (B, F, n_bins) f32,
+    voiced (B, F) f64, unvoiced (B, F) f32, n_frames (B) int64)``, F = 1 + S // hop,
+    ``n_bins`` as ``audio.pyin_tables`` counts them; zeros past ``n_frames``."""
+    _rows_f32("f0_pyin_candidates", wav, lens)
+    B, S = wav.shape
+    hop, dev = _pyin_hop("f0_pyin_candidates", hop), wav.device
+    _pyin_table("f0_pyin_candidates", "prior", prior, torch.float64, 100, dev)
+    F, nb = 1 + S // hop, int(n_bins)
+    if not 1 <= nb <= 1024:
+        raise RuntimeError(f"f0_pyin_candidates: {nb} pitch bins (1..1024)")
+    mass = torch.empty((B, F, nb), dtype=torch.float64, device=dev)
+    cf0 = torch.empty((B, F, nb), dtype=torch.float32, device=dev)
+    voiced = torch.empty((B, F), dtype=torch.float64, device=dev)
+    unvoiced = torch.empty((B, F), dtype=torch.float32, device=dev)
+    nf = torch.empty(B, dtype=torch.int64, device=dev)
+    lib.fs2_f0_pyin_candidates(ptr(wav), ptr(lens), B, S, hop, float(sr), float(f0_floor),
+                               float(f0_ceil), ptr(prior), nb, ptr(mass), ptr(cf0), ptr(voiced),
+                               ptr(unvoiced), ptr(nf), stream())
+    return mass, cf0, voiced, unvoiced, nf
+
+
+def f0_pyin_viterbi(mass, voiced, n_frames, tri, cand_f0=None, centres=None):
+    """The second stage of pYIN (fs2_f0_pyin_viterbi): mass (B, F, n_bins) f64, voiced (B, F) f64,
+    n_frames device int64 (B) or None, ``tri`` device f64 (R + 1) -> ``path (B, F) int32`` (state
+    b = voiced bin b, n_bins + b = unvoiced; -1 past ``n_frames``); with ``cand_f0`` (B, F, n_bins)
+    f32 and ``centres`` (n_bins) f32 also the contour: ``(path, f0 (B, F) f32)``."""
+    _dev(mass, voiced, n_frames, tri, cand_f0, centres)
+    if mass.dtype != torch.float64 or mass.dim() != 3 or voiced.dtype != torch.float64 or \
+            tuple(voiced.shape) != tuple(mass.shape[:2]):
+        raise RuntimeError("f0_pyin_viterbi: mass (B, F, n_bins) and voiced (B, F) are f64")
+    B, F, nb = mass.shape
+    dev = mass.device
+    if n_frames is not None:
+        _lens_i64("f0_pyin_viterbi", n_frames, B)
+    if tri.dtype != torch.float64 or tri.dim() != 1 or tri.numel() < 1:
+        raise RuntimeError("f0_pyin_viterbi: tri is f64 (R + 1)")
+    if (cand_f0 is None) != (centres is None):
+        raise RuntimeError("f0_pyin_viterbi: cand_f0 and centres come as a pair or not at all")
+    f0 = None
+    if cand_f0 is not None:
+        if cand_f0.dtype != torch.float32 or tuple(cand_f0.shape) != (B, F, nb):
+            raise RuntimeError(f"f0_pyin_viterbi: cand_f0 is f32 ({B}, {F}, {nb})")
+        _pyin_table("f0_pyin_viterbi", "centres", centres, torch.float32, nb, dev)
+        f0 = torch.empty((B, F), dtype=torch.float32, device=dev)
+    path = torch.empty((B, F), dtype=torch.int32, device=dev)
+    nbytes = lib.fs2_f0_pyin_viterbi_ws_bytes(B, F, nb)
+    wk = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    lib.fs2_f0_pyin_viterbi(ptr(mass), ptr(voiced), ptr(n_frames), B, F, nb, ptr(tri),
+                            tri.numel() - 1, ptr(cand_f0), ptr(centres), ptr(path), ptr(f0), ptr(wk),
+                            nbytes, stream())
+    return path if f0 is None else (path, f0)
+
+
+def f0_pyin(wav, lens, hop, sr, f0_floor, f0_ceil, prior, tri, centres, out=None, states=False):
+    """The pYIN F0 contour of a ragged batch (fs2_f0_pyin): wav (B, S) f32, lens device int64 (B)
+    or None; the device tables of ``audio.pyin_tables``: ``prior`` f64 (100), ``tri`` f64 (R + 1),
+    ``centres`` f32 (n_bins) -> ``(f0 (B, F), unvoiced (B, F), n_frames (B) int64)``,
+    F = 1 + S // hop, zeros past ``n_frames``; ``unvoiced`` = 1 - the voiced prior mass (small
+    means strongly periodic).  ``out`` = preallocated ``(f0, unvoiced, n_frames)``;
+    ``states=True`` appends the decoded states (B, F) int32."""
+    _rows_f32("f0_pyin", wav, lens)
+    B, S = wav.shape
+    hop, dev = _pyin_hop("f0_pyin", hop), wav.device
+    _pyin_table("f0_pyin", "prior", prior, torch.float64, 100, dev)
+    _dev(tri, centres)
+    if tri.dtype != torch.float64 or tri.dim() != 1 or tri.numel() < 1:
+        raise RuntimeError("f0_pyin: tri is f64 (R + 1)")
+    if centres.dtype != torch.float32 or centres.dim() != 1 or centres.numel() < 1:
+        raise RuntimeError("f0_pyin: centres is f32 (n_bins)")
+    F, nb = 1 + S // hop, centres.numel()
+    if out is None:
+        out = (torch.empty((B, F), dtype=torch.float32, device=dev),
+               torch.empty((B, F), dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int64, device=dev))
+    f0, unv, nf = out
+    _dev(f0, unv, nf)
+    if f0.dtype != torch.float32 or unv.dtype != torch.float32 or f0.numel() != B * F or \
+            unv.numel() != B * F or nf.dtype != torch.int64 or nf.numel() != B:
+        raise RuntimeError("f0_pyin: out is (f0 (B, F), unvoiced (B, F)) f32 and n_frames (B) int64")
+    st = torch.empty((B, F), dtype=torch.int32, device=dev) if states else None
+    nbytes = lib.fs2_f0_pyin_ws_bytes(B, S, hop, nb)
+    wk = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    lib.fs2_f0_pyin(ptr(wav), ptr(lens), B, S, hop, float(sr), float(f0_floor), float(f0_ceil),
+                    ptr(prior), ptr(tri), tri.numel() - 1, ptr(centres), nb, ptr(f0), ptr(unv),
+                    ptr(nf), ptr(st), ptr(wk), nbytes, stream())
+    return (f0, unv, nf, st) if states else (f0, unv, nf)
+
+
 def resample(wav, lens, table, up, down, half, first=None, count=None, out_samples=None, out=None):
     """Rational polyphase resampling of a ragged batch (fs2_resample): wav (B, S) f32, lens
     device int64 (B) or None, table device f32 (2 half + 1) = L h (audio.resample_filter),

@@ -13,8 +13,10 @@ on the device: a waveform and its alignment give the mel, pitch, energy and dura
                       307-315, 94-97, 317-328, 126-141   ``CorpusStats``
 
 The F0 contour is the one thing that is not the reference's: pyworld (DIO + StoneMask) is
-replaced by the YIN of ``audio.PitchExtractor``.  Everything after the contour follows the
-reference line for line, and every entry point takes ``f0=`` for contours made elsewhere.
+replaced by the YIN of ``audio.PitchExtractor``, or with ``pitch_method="pyin"`` by its pYIN
+(threshold-distribution YIN with a Viterbi track: steadier voicing in noise).  Everything after
+the contour follows the reference line for line whichever method made it, and every entry point
+takes ``f0=`` for contours made elsewhere.
 
 Quirk kept: the phoneme-level average writes ``pitch[i]`` while later phonemes still read the
 same array (lines 224-231); after zero durations ``pos`` falls behind ``i`` and a later phoneme
@@ -88,15 +90,18 @@ class FeatureExtractor:
       ok        (B) int32        0 where the reference returns None (at most one voiced frame,
                                  line 204); such a row's pitch is not interpolated
 
-    ``f0`` (B, >= T) replaces the estimator (which reads the unclipped samples, line 196)."""
+    ``f0`` (B, >= T) replaces the estimator (which reads the unclipped samples, line 196).
+    ``pitch_method`` is ``PitchExtractor``'s ``method``: ``"yin"`` or ``"pyin"`` (which ignores
+    ``threshold``)."""
 
     def __init__(self, preprocess_config=None, device="cuda", f0_floor=71.0, f0_ceil=800.0,
-                 threshold=0.15):
+                 threshold=0.15, pitch_method="yin"):
         pp = preprocess_config if preprocess_config is not None else load_configs()[0]
         self.pp = pp
         self.device = torch.device(device)
         self.front = MelFrontEnd(pp, device)
-        self.pitcher = PitchExtractor(pp, device, f0_floor, f0_ceil, threshold)
+        self.pitcher = PitchExtractor(pp, device, f0_floor, f0_ceil, threshold,
+                                      method=pitch_method)
         self.hop, self.sr = self.front.hop, self.front.sr
         for name in ("pitch", "energy"):
             level = pp[name]["feature"]
@@ -253,12 +258,13 @@ class Preprocessor:
 
     Differences from the reference, all deliberate: speakers and files are walked in sorted
     order (``os.listdir`` order there) and the split is drawn from ``random.Random(seed)``; the
-    F0 contour is ``audio.PitchExtractor``'s unless ``f0_dir`` holds
+    F0 contour is ``audio.PitchExtractor``'s (``pitch_method`` = ``"yin"`` or ``"pyin"``) unless
+    ``f0_dir`` holds
     ``<speaker>-f0-<basename>.npy`` contours of the trimmed waveforms; pitch and energy are
     stored as float32."""
 
     def __init__(self, config, device="cuda", batch=16, seed=None, f0_dir=None,
-                 keep_bytes=1 << 30):
+                 keep_bytes=1 << 30, pitch_method="yin"):
         self.config = config
         self.in_dir = config["path"]["raw_path"]
         self.out_dir = config["path"]["preprocessed_path"]
@@ -273,7 +279,8 @@ class Preprocessor:
         self.keep_bytes = int(keep_bytes)
         if self.batch < 1:
             raise ValueError(f"batch {batch}")
-        self.extractor = FeatureExtractor(pp, device)  # checks pitch.feature / energy.feature
+        # checks pitch.feature / energy.feature and the pitch method
+        self.extractor = FeatureExtractor(pp, device, pitch_method=pitch_method)
         self.pitch_phoneme_averaging = self.extractor.pitch_phoneme
         self.energy_phoneme_averaging = self.extractor.energy_phoneme
         self.resampler = Resampler(self.sampling_rate, device)
@@ -478,7 +485,8 @@ def write_split(out, out_dir, val_size, test_size, seed=None):
 
 
 def main(argv=None):
-    """The reference's ``preprocess.py``: ``--config DIR [--corpus NAME]`` reads
+    """The reference's ``preprocess.py``: ``--config DIR [--corpus NAME] [--pitch_method
+    {yin,pyin}]`` reads
     ``DIR/preprocess.yaml`` (with its two ``normalization = False`` overrides) and
     ``DIR/preprocess_<corpus>.yaml``, every ``preprocess_*.yaml`` without ``--corpus``."""
     import argparse
@@ -489,6 +497,9 @@ def main(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--config", type=str, required=True, help="path to config")
     parser.add_argument("--corpus", type=str, default=None, help="corpus name")
+    parser.add_argument("--pitch_method", choices=PitchExtractor.METHODS, default="yin",
+                        help="the F0 estimator: plain YIN, or pYIN (threshold distribution + "
+                             "Viterbi track)")
     args = parser.parse_args(argv)
     with open(os.path.join(args.config, "preprocess.yaml")) as f:
         preprocess_config = yaml.safe_load(f)
@@ -504,7 +515,7 @@ def main(argv=None):
         config["preprocessing"] = preprocess_config
         config["preprocessing"]["text"] = config["text"]
         print("preprocessing...:", config["dataset"])
-        Preprocessor(config).build_from_path()
+        Preprocessor(config, pitch_method=args.pitch_method).build_from_path()
 
 
 if __name__ == "__main__":

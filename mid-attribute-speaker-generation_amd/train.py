@@ -726,7 +726,8 @@ def load_discriminator(train_config, device):
 
 def main(argv=None):
     """``python -m mid-attribute-speaker-generation_amd.train -c DIR [--restore_step N]
-    [--checkpoint P] [--corpus NAME ...] [--use_clf] [--synth_metrics]`` (``train.py:296-343``).  ``DIR`` holds
+    [--checkpoint P] [--corpus NAME ...] [--use_clf] [--synth_metrics] [--synth_pitch {yin,pyin}]``
+    (``train.py:296-343``).  ``DIR`` holds
     ``preprocess.yaml``, ``model.yaml``, ``train.yaml``, ``stats.json``, ``speakers.json`` and one
     ``preprocess_<corpus>.yaml`` per corpus (all of them in sorted order, or the ``--corpus``
     ones in the order given).  ``--dtype bf16`` runs the bf16 compute path."""
@@ -752,6 +753,8 @@ def main(argv=None):
     ap.add_argument("--synth_metrics", action="store_true",
                     help="every synth_step, log MCD, length, F0 and V/UV error of free-running "
                          "synthesis against the validation corpus (evaluate_synthesis)")
+    ap.add_argument("--synth_pitch", choices=("yin", "pyin"), default="yin",
+                    help="the F0 estimator behind --synth_metrics' F0 and V/UV errors")
     args = ap.parse_args(argv)
 
     pp, mc, tc, path = cfg.load_configs(args.config)
@@ -806,8 +809,8 @@ def main(argv=None):
             vocoder = get_vocoder(device="cuda", ckpt=voc_ckpt)
         else:
             vocoder = GriffinLim(front_end=front_end)
-        synth_eval = dict(vocoder=vocoder, pitch=PitchExtractor(pp, device="cuda"),
-                          front_end=front_end)
+        pitch = PitchExtractor(pp, device="cuda", method=args.synth_pitch)
+        synth_eval = dict(vocoder=vocoder, pitch=pitch, front_end=front_end)
     print("Number of FastSpeech2 Parameters:", sum(p.numel() for p in model.parameters()))
     last = fit(trainer, CorpusBatcher(train_store, bs), CorpusBatcher(
         val_store, bs, group_size=1, shuffle=False, sort=False, drop_last=False), tc,
