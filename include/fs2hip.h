@@ -87,6 +87,22 @@ int fs2_conv_gemm_ln(const void* x, int64_t ldx, const void* wk, int64_t rows, i
                      const float* bias, const float* res, const float* gamma, const float* beta,
                      float* out, void* out_t, float* xhat, float* rstd, float p_in,
                      const uint64_t* seed, uint64_t site_in, void* stream);
+/* The same with the residual in either of two forms: res (fp32, as above), or the LayerNorm
+ * that produced it -- res_xhat (rows, 256) with res_gamma / res_beta (256,), masked by the same
+ * lens: the residual of row r is res_xhat[r] * res_gamma + res_beta where t < lens[b] and 0
+ * where t >= lens[b] (res_xhat is not read there: its producer left those rows unwritten).
+ * The producer is a post-LN site (fs2_conv_gemm_ln, or fs2_ln_fwd with p_out = 0, no head).
+ * The rebuilt value has the bits that producer wrote (or would have written) to its `out`, so
+ * a stack of post-LN sites need not store the fp32 `out` at all: out may be NULL here and in
+ * fs2_conv_gemm_ln (no fp32 store; out_t, xhat and rstd as usual).  Give res or the triple,
+ * not both.                                                                               */
+int fs2_conv_gemm_ln_nres(const void* x, int64_t ldx, const void* wk, int64_t rows,
+                          int64_t seq_len, int64_t c_in, int64_t c_out, int taps, int pad,
+                          const int64_t* lens, const float* bias, const float* res,
+                          const float* res_xhat, const float* res_gamma, const float* res_beta,
+                          const float* gamma, const float* beta, float* out, void* out_t,
+                          float* xhat, float* rstd, float p_in, const uint64_t* seed,
+                          uint64_t site_in, void* stream);
 
 /* bf16 Linear / Conv1d (c_out = 256) whose output is the upstream gradient of a post-
  * LayerNorm, with that LayerNorm's backward in the epilogue:
@@ -767,6 +783,25 @@ int64_t fs2_fft_block_act_offset(const int64_t* blk, int64_t rows, int64_t batch
 int fs2_fft_block_fwd(const int64_t* blk, const float* x, const void* x_t, void* act, int64_t rows,
                       int64_t batch, int64_t seq_len, const int64_t* lens, float p,
                       const uint64_t* seed, int fuse_ln, void* stream);
+/* A block inside a stack.  The fp32 residual stream between post-LN sites is not stored: the
+ * w_2 site rebuilds LN1's output from the saved xhat, and with prev_blk / prev_act (the block
+ * before this one and its act region, same rows / lens; x NULL) the fc site rebuilds the block
+ * input from that block's LN2 the same way (fs2_conv_gemm_ln_nres: bitwise the stored value).
+ * The first block of a stack passes x (prev_blk NULL).  store_x2: also write the fp32 block
+ * output -- for a reader outside the stack (the encoder's last block; a single block).  Without
+ * it the region has no FS2_FA_X2 tensor (fs2_fft_block_act_offset_x2 returns -1 for it) and is
+ * rows * d * 4 bytes smaller; every other offset is the same either way, and the backward
+ * reads neither.  fs2_fft_block_fwd / _act_bytes / _act_offset are the store_x2 = 1, prev_blk =
+ * NULL forms.                                                                               */
+int64_t fs2_fft_block_act_bytes_x2(const int64_t* blk, int64_t rows, int64_t batch,
+                                   int64_t seq_len, int fuse_ln, int store_x2);
+int64_t fs2_fft_block_act_offset_x2(const int64_t* blk, int64_t rows, int64_t batch,
+                                    int64_t seq_len, int fuse_ln, int store_x2, int which);
+int fs2_fft_block_fwd_nres(const int64_t* blk, const float* x, const void* x_t,
+                           const int64_t* prev_blk, const void* prev_act, int prev_fuse_ln,
+                           int store_x2, void* act, int64_t rows, int64_t batch, int64_t seq_len,
+                           const int64_t* lens, float p, const uint64_t* seed, int fuse_ln,
+                           void* stream);
 /* Backward from dx2 (the output gradient) or from (carry_dy2_t, carry_dx1), the block's LN2
  * backward already done by the following block.  dx (rows, d) fp32: the input gradient, or,
  * with prev_blk (the block before this one, its act region), that block's LN2 backward runs in
@@ -914,6 +949,15 @@ int fs2_ln_fwd(int dtype, const float* y, const float* res, const float* gamma, 
                const uint64_t* seed, uint64_t site_in, uint64_t site_out, const float* dot_w,
                const float* dot_b,
                float* dot_out, void* stream);
+/* fs2_ln_fwd with the residual as res (fp32) or as the LayerNorm that produced it (res_xhat,
+ * res_gamma, res_beta; masked by the same lens and never read on masked rows): see
+ * fs2_conv_gemm_ln_nres.  out may be NULL here and in fs2_ln_fwd: no fp32 store.          */
+int fs2_ln_fwd_nres(int dtype, const float* y, const float* res, const float* res_xhat,
+                    const float* res_gamma, const float* res_beta, const float* gamma,
+                    const float* beta, float* out, void* out_t, float* xhat, float* rstd,
+                    const int64_t* lens, int64_t seq_len, int64_t rows, int d, float p_in,
+                    float p_out, const uint64_t* seed, uint64_t site_in, uint64_t site_out,
+                    const float* dot_w, const float* dot_b, float* dot_out, void* stream);
 /* Backward of fs2_ln_fwd.  Upstream gradient is dout (per element) or, in dot mode,
  * ddot (per row).  Produces dy (gradient w.r.t. y before dropout, times (relu_y > 0) when
  * relu_y != NULL), optionally adds dz into dres (dres_add 1: +=, 0: =), and accumulates dgamma, dbeta and

@@ -79,11 +79,14 @@ Blk unpack(const int64_t* w) {
 
 int64_t al(int64_t bytes) { return (bytes + 255) / 256 * 256; }
 
-// the forward's activation region: offsets (bytes) of its tensors
+// the forward's activation region: offsets (bytes) of its tensors.  The fp32 LN1 output is
+// never stored (the w_2 site rebuilds its residual from xh1), the fp32 block output x2 only on
+// request and last, so that no other offset depends on it (the backward reads neither).
 struct ActLayout {
-  int64_t qkv, o, lse, x1, x1_t, xh1, rs1, h, x2, x2_t, xh2, rs2, y, total;
+  int64_t qkv, o, lse, x1_t, xh1, rs1, h, x2, x2_t, xh2, rs2, y, total;
 };
-ActLayout act_layout(const Blk& b, int64_t rows, int64_t batch, int64_t T, int fuse) {
+ActLayout act_layout(const Blk& b, int64_t rows, int64_t batch, int64_t T, int fuse,
+                     int store_x2 = 0) {
   ActLayout L;
   int64_t o = 0;
   auto take = [&](int64_t bytes) {
@@ -94,16 +97,15 @@ ActLayout act_layout(const Blk& b, int64_t rows, int64_t batch, int64_t T, int f
   L.qkv = take(rows * b.n3 * 2);
   L.o = take(rows * b.hd * 2);
   L.lse = take(batch * b.heads * T * 4);
-  L.x1 = take(rows * b.d * 4);
   L.x1_t = take(rows * b.d * 2);
   L.xh1 = take(rows * b.d * 4);
   L.rs1 = take(rows * 4);
   L.h = take(rows * b.dinner * 2);
-  L.x2 = take(rows * b.d * 4);
   L.x2_t = take(rows * b.d * 2);
   L.xh2 = take(rows * b.d * 4);
   L.rs2 = take(rows * 4);
   L.y = fuse ? -1 : take(rows * b.d * 4);  // fp32 GEMM output before a separate LayerNorm
+  L.x2 = store_x2 ? take(rows * b.d * 4) : -1;
   L.total = o;
   return L;
 }
@@ -154,12 +156,22 @@ extern "C" {
 
 int64_t fs2_fft_block_act_bytes(const int64_t* blk, int64_t rows, int64_t batch, int64_t seq_len,
                                 int fuse_ln) {
-  return act_layout(unpack(blk), rows, batch, seq_len, fuse_ln).total;
+  return fs2_fft_block_act_bytes_x2(blk, rows, batch, seq_len, fuse_ln, 1);
+}
+
+int64_t fs2_fft_block_act_bytes_x2(const int64_t* blk, int64_t rows, int64_t batch,
+                                   int64_t seq_len, int fuse_ln, int store_x2) {
+  return act_layout(unpack(blk), rows, batch, seq_len, fuse_ln, store_x2).total;
 }
 
 int64_t fs2_fft_block_act_offset(const int64_t* blk, int64_t rows, int64_t batch,
                                  int64_t seq_len, int fuse_ln, int which) {
-  const ActLayout L = act_layout(unpack(blk), rows, batch, seq_len, fuse_ln);
+  return fs2_fft_block_act_offset_x2(blk, rows, batch, seq_len, fuse_ln, 1, which);
+}
+
+int64_t fs2_fft_block_act_offset_x2(const int64_t* blk, int64_t rows, int64_t batch,
+                                    int64_t seq_len, int fuse_ln, int store_x2, int which) {
+  const ActLayout L = act_layout(unpack(blk), rows, batch, seq_len, fuse_ln, store_x2);
   switch (which) {
     case FS2_FA_X2: return L.x2;
     case FS2_FA_X2_T: return L.x2_t;
@@ -184,10 +196,30 @@ int64_t fs2_fft_block_side_ws_bytes(const int64_t* blk, int64_t rows) {
 int fs2_fft_block_fwd(const int64_t* blk, const float* x, const void* x_t, void* act, int64_t rows,
                       int64_t batch, int64_t seq_len, const int64_t* lens, float p,
                       const uint64_t* seed, int fuse_ln, void* stream) {
-  FS2_CHECK_ARG(blk && x && x_t && act && rows == batch * seq_len && seq_len > 0,
+  return fs2_fft_block_fwd_nres(blk, x, x_t, nullptr, nullptr, 0, 1, act, rows, batch, seq_len,
+                                lens, p, seed, fuse_ln, stream);
+}
+
+int fs2_fft_block_fwd_nres(const int64_t* blk, const float* x, const void* x_t,
+                           const int64_t* prev_blk, const void* prev_act, int prev_fuse_ln,
+                           int store_x2, void* act, int64_t rows, int64_t batch, int64_t seq_len,
+                           const int64_t* lens, float p, const uint64_t* seed, int fuse_ln,
+                           void* stream) {
+  FS2_CHECK_ARG(blk && x_t && act && rows == batch * seq_len && seq_len > 0,
                 "fs2_fft_block_fwd: bad arguments");
+  FS2_CHECK_ARG((x != nullptr) != (prev_blk != nullptr && prev_act != nullptr),
+                "fs2_fft_block_fwd: give x or the previous block (prev_blk, prev_act), not both");
   const Blk b = unpack(blk);
-  const ActLayout L = act_layout(b, rows, batch, seq_len, fuse_ln);
+  const ActLayout L = act_layout(b, rows, batch, seq_len, fuse_ln, store_x2);
+  // the residual stream entering the block: x, or the previous block's LN2 (its xh2 and affine)
+  const float *rx = nullptr, *rg = nullptr, *rb = nullptr;
+  if (prev_blk) {
+    const Blk pb = unpack(prev_blk);
+    rx = at<const float>(const_cast<void*>(prev_act),
+                         act_layout(pb, rows, batch, seq_len, prev_fuse_ln).xh2);
+    rg = pb.ln2_g;
+    rb = pb.ln2_b;
+  }
   const int64_t T = seq_len;
   const uint64_t* sd = p > 0.f ? seed : nullptr;
   FS2_CHECK_ARG(!(p > 0.f) || seed, "fs2_fft_block_fwd: dropout without seed");
@@ -195,12 +227,11 @@ int fs2_fft_block_fwd(const int64_t* blk, const float* x, const void* x_t, void*
   void* qkv = at<void>(act, L.qkv);
   void* o = at<void>(act, L.o);
   float* lse = at<float>(act, L.lse);
-  float* x1 = at<float>(act, L.x1);
   void* x1_t = at<void>(act, L.x1_t);
   float* xh1 = at<float>(act, L.xh1);
   float* rs1 = at<float>(act, L.rs1);
   void* h = at<void>(act, L.h);
-  float* x2 = at<float>(act, L.x2);
+  float* x2 = store_x2 ? at<float>(act, L.x2) : nullptr;
   void* x2_t = at<void>(act, L.x2_t);
   float* xh2 = at<float>(act, L.xh2);
   float* rs2 = at<float>(act, L.rs2);
@@ -211,29 +242,32 @@ int fs2_fft_block_fwd(const int64_t* blk, const float* x, const void* x_t, void*
   FS2_TRY(fs2_attn_fwd(FS2_BF16, qkv, o, lse, lens, batch, T, (int)b.heads, (int)b.dk, scale, stream));
   // fc -> dropout -> + residual -> LayerNorm, masked (SubLayers.py:53-55, Layers.py:25)
   if (fuse_ln) {
-    FS2_TRY(fs2_conv_gemm_ln(o, b.hd, b.wfc_f, rows, T, b.hd, b.d, 1, 0, lens, b.bfc, x, b.ln1_g,
-                             b.ln1_b, x1, x1_t, xh1, rs1, p, sd, (uint64_t)b.site, stream));
+    FS2_TRY(fs2_conv_gemm_ln_nres(o, b.hd, b.wfc_f, rows, T, b.hd, b.d, 1, 0, lens, b.bfc, x, rx, rg,
+                                  rb, b.ln1_g, b.ln1_b, nullptr, x1_t, xh1, rs1, p, sd,
+                                  (uint64_t)b.site, stream));
   } else {
     float* y = at<float>(act, L.y);
     FS2_TRY(fs2_conv_gemm(FS2_BF16, o, b.hd, b.wfc_f, y, b.d, rows, T, b.hd, b.d, 1, 0, lens, b.bfc,
                           FS2_EPI_BIAS, nullptr, b.d, stream));
-    FS2_TRY(fs2_ln_fwd(FS2_BF16, y, x, b.ln1_g, b.ln1_b, x1, x1_t, xh1, rs1, lens, T, rows, (int)b.d,
-                       p, 0.f, sd, (uint64_t)b.site, 0, nullptr, nullptr, nullptr, stream));
+    FS2_TRY(fs2_ln_fwd_nres(FS2_BF16, y, x, rx, rg, rb, b.ln1_g, b.ln1_b, nullptr, x1_t, xh1, rs1,
+                            lens, T, rows, (int)b.d, p, 0.f, sd, (uint64_t)b.site, 0, nullptr,
+                            nullptr, nullptr, stream));
   }
   // Conv1d(k) -> ReLU -> Conv1d(1) -> dropout -> + residual -> LayerNorm (SubLayers.py:85-93)
   FS2_TRY(fs2_conv_gemm(FS2_BF16, x1_t, b.d, b.w1_f, h, b.dinner, rows, T, b.d, b.dinner, (int)b.taps,
                         (int)b.pad, lens, b.b1, FS2_EPI_BIAS | FS2_EPI_RELU | FS2_EPI_OUT_BF16, nullptr,
                         b.dinner, stream));
   if (fuse_ln) {
-    FS2_TRY(fs2_conv_gemm_ln(h, b.dinner, b.w2_f, rows, T, b.dinner, b.d, 1, 0, lens, b.b2, x1,
-                             b.ln2_g, b.ln2_b, x2, x2_t, xh2, rs2, p, sd, (uint64_t)(b.site + 1),
-                             stream));
+    FS2_TRY(fs2_conv_gemm_ln_nres(h, b.dinner, b.w2_f, rows, T, b.dinner, b.d, 1, 0, lens, b.b2,
+                                  nullptr, xh1, b.ln1_g, b.ln1_b, b.ln2_g, b.ln2_b, x2, x2_t, xh2,
+                                  rs2, p, sd, (uint64_t)(b.site + 1), stream));
   } else {
     float* y = at<float>(act, L.y);
     FS2_TRY(fs2_conv_gemm(FS2_BF16, h, b.dinner, b.w2_f, y, b.d, rows, T, b.dinner, b.d, 1, 0, lens,
                           b.b2, FS2_EPI_BIAS, nullptr, b.d, stream));
-    FS2_TRY(fs2_ln_fwd(FS2_BF16, y, x1, b.ln2_g, b.ln2_b, x2, x2_t, xh2, rs2, lens, T, rows, (int)b.d,
-                       p, 0.f, sd, (uint64_t)(b.site + 1), 0, nullptr, nullptr, nullptr, stream));
+    FS2_TRY(fs2_ln_fwd_nres(FS2_BF16, y, nullptr, xh1, b.ln1_g, b.ln1_b, b.ln2_g, b.ln2_b, x2, x2_t,
+                            xh2, rs2, lens, T, rows, (int)b.d, p, 0.f, sd, (uint64_t)(b.site + 1),
+                            0, nullptr, nullptr, nullptr, stream));
   }
   return FS2_OK;
 }

@@ -78,7 +78,8 @@ int conv_gemm_bf16_launch(const void* x, int64_t ldx, const void* wk, void* y, i
                           const void* aux, int64_t ld_aux, const VocEpi& ve, hipStream_t st);
 int conv_gemm_ln_glds_launch(const void* x, int64_t ldx, const void* wk, int64_t rows,
                              int64_t seq_len, int64_t c_in, int taps, int pad, const int64_t* lens,
-                             const float* bias, const float* res, const float* gamma,
+                             const float* bias, const float* res, const float* res_xhat,
+                             const float* res_gamma, const float* res_beta, const float* gamma,
                              const float* beta, float* out, void* out_t, float* xhat, float* rstd,
                              float p_in, const uint64_t* seed, uint64_t site_in, hipStream_t st);
 int conv_gemm_lnbwd_glds_launch(const void* x, int64_t ldx, const void* wk, int64_t rows,
@@ -247,6 +248,16 @@ FS2_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 FS2_DEV void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 FS2_DEV int div_up(int a, int b) { return (a + b - 1) / b; }
+
+// LayerNorm affine of 4 channels, out = xhat * gamma + beta, as ONE fused multiply-add per
+// element (what the forward kernels compiled to before it was pinned).  The kernels that write
+// `out` and the kernels that rebuild it from a saved xhat (the normalised-residual input of
+// fs2_ln_fwd_nres / fs2_conv_gemm_ln_nres) both call this, so the rebuilt value has the bits
+// of the stored one whatever the compiler would have contracted at either site.
+FS2_DEV f32x4 ln_affine(f32x4 xh, f32x4 ga, f32x4 be) {
+  return f32x4{__fmaf_rn(xh.x, ga.x, be.x), __fmaf_rn(xh.y, ga.y, be.y),
+               __fmaf_rn(xh.z, ga.z, be.z), __fmaf_rn(xh.w, ga.w, be.w)};
+}
 
 // bf16 compute copies (round to nearest even; gfx950 v_cvt_pk_bf16_f32)
 FS2_DEV unsigned short to_bf16(float f) {

@@ -61,18 +61,22 @@ int conv_gemm_bf16_launch(const void* x, int64_t ldx, const void* wk, void* y, i
 // fs2_conv_gemm_ln: the tap-major kernel on whole 256-wide rows with the LayerNorm epilogue
 int conv_gemm_ln_glds_launch(const void* x, int64_t ldx, const void* wk, int64_t rows,
                              int64_t seq_len, int64_t c_in, int taps, int pad, const int64_t* lens,
-                             const float* bias, const float* res, const float* gamma,
+                             const float* bias, const float* res, const float* res_xhat,
+                             const float* res_gamma, const float* res_beta, const float* gamma,
                              const float* beta, float* out, void* out_t, float* xhat, float* rstd,
                              float p_in, const uint64_t* seed, uint64_t site_in, hipStream_t st) {
   FS2_CHECK_ARG(c_in % 8 == 0 && ldx % 8 == 0 && al16(x) && al16(wk),
                 "fs2_conv_gemm_ln: c_in/ldx must be multiples of 8 and operands 16-B aligned");
   FS2_CHECK_ARG(al16(out) && al16(xhat) && al16(gamma) && al16(beta) && al16(res) && al16(bias) &&
-                    al16(out_t),
+                    al16(out_t) && al16(res_xhat) && al16(res_gamma) && al16(res_beta),
                 "fs2_conv_gemm_ln: LayerNorm tensors must be 16-B aligned");
   GldsArgs a{(const u16*)x, ldx, (const u16*)wk, nullptr, 256, rows, seq_len, (int)c_in, 256,
              taps, pad, (int)(taps * c_in), bias, bias ? FS2_EPI_BIAS : 0, nullptr, 0, 0, 0, 1, 1,
              lens, 1, 0.f, 1.f, nullptr, 0.f};
   a.ln_res = res;
+  a.ln_res_xhat = res_xhat;
+  a.ln_res_gamma = res_gamma;
+  a.ln_res_beta = res_beta;
   a.ln_gamma = gamma;
   a.ln_beta = beta;
   a.ln_out = out;

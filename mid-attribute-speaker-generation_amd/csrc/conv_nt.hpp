@@ -27,7 +27,9 @@ struct GldsArgs {
   float alpha2;
   int kz;               // halo kernel: channel-block splits (0/1 = none; see halo_splitk_reduce)
   float* slab;          // kz > 1: [kz][M][N] fp32 partial products
-  // LayerNorm epilogue (fs2_conv_gemm_ln; 256-wide tiles hold whole rows): ln_out != NULL
+  // LayerNorm epilogue (fs2_conv_gemm_ln; 256-wide tiles hold whole rows): ln_xhat != NULL.
+  // The residual is ln_res (fp32) or, rebuilt per row, ln_res_xhat * ln_res_gamma + ln_res_beta
+  // (0 on rows masked by lens); ln_out NULL: no fp32 store
   const float* ln_res;
   const float* ln_gamma;
   const float* ln_beta;
@@ -44,6 +46,9 @@ struct GldsArgs {
   int ln_dres_add;
   float* ln_part;
   int64_t ln_nblk;
+  const float* ln_res_xhat;
+  const float* ln_res_gamma;
+  const float* ln_res_beta;
 };
 
 // With lens (all-padding row tiles skipped) the XCD-contiguous tile order would give each XCD
@@ -72,6 +77,8 @@ FS2_DEV int m_interleave(int tm, int tiles_m, bool on) {
 // over the half-wave's 256 channels (8 per lane, the fs2_ln_fwd lane layout), out = xhat *
 // gamma + beta, padded rows written as 0 (xhat / rstd not written there: the backward skips
 // them).  Same operations in the same order as fs2_conv_gemm + fs2_ln_fwd: bitwise equal.
+// A normalised residual (ln_res_xhat) is read only on the rows that pass the lens test: its
+// producer left xhat unwritten on the others, where the residual is 0.
 template <int BM, int NWAVE, int WN>
 FS2_DEV void nt_epilogue_ln(const GldsArgs& a, f32x4 (&acc)[BM / 32][256 / WN / 16], u16* smem,
                             int64_t m0, bool skip, int tid, int wm, int wn, int g, int r16) {
@@ -82,6 +89,13 @@ FS2_DEV void nt_epilogue_ln(const GldsArgs& a, f32x4 (&acc)[BM / 32][256 / WN / 
   const uint64_t seed = a.ln_seed ? *a.ln_seed : 0ull;
   const f32x4 ga0 = ld4(a.ln_gamma + 8 * hl), ga1 = ld4(a.ln_gamma + 8 * hl + 4);
   const f32x4 be0 = ld4(a.ln_beta + 8 * hl), be1 = ld4(a.ln_beta + 8 * hl + 4);
+  f32x4 rg0 = f32x4{0.f, 0.f, 0.f, 0.f}, rg1 = rg0, rb0 = rg0, rb1 = rg0;
+  if (a.ln_res_xhat && !skip) {
+    rg0 = ld4(a.ln_res_gamma + 8 * hl);
+    rg1 = ld4(a.ln_res_gamma + 8 * hl + 4);
+    rb0 = ld4(a.ln_res_beta + 8 * hl);
+    rb1 = ld4(a.ln_res_beta + 8 * hl + 4);
+  }
   f32x4 bi0 = f32x4{0.f, 0.f, 0.f, 0.f}, bi1 = bi0;
   if ((a.flags & FS2_EPI_BIAS) && !skip) {
     bi0 = ld4(a.bias + 8 * hl);
@@ -108,8 +122,10 @@ FS2_DEV void nt_epilogue_ln(const GldsArgs& a, f32x4 (&acc)[BM / 32][256 / WN / 
       const bool pad = a.lens && (m % a.T) >= a.lens[m / a.T];
       if (pad) {
         const f32x4 zz = {0.f, 0.f, 0.f, 0.f};
-        st4(a.ln_out + e0, zz);
-        st4(a.ln_out + e0 + 4, zz);
+        if (a.ln_out) {
+          st4(a.ln_out + e0, zz);
+          st4(a.ln_out + e0 + 4, zz);
+        }
         if (a.ln_out_t) st8_bf16(a.ln_out_t + e0, zz, zz);
         continue;
       }
@@ -126,6 +142,9 @@ FS2_DEV void nt_epilogue_ln(const GldsArgs& a, f32x4 (&acc)[BM / 32][256 / WN / 
       if (a.ln_res) {
         z0 += ld4(a.ln_res + e0);
         z1 += ld4(a.ln_res + e0 + 4);
+      } else if (a.ln_res_xhat) {  // this row is valid (the padded ones left above)
+        z0 += ln_affine(ld4(a.ln_res_xhat + e0), rg0, rb0);
+        z1 += ln_affine(ld4(a.ln_res_xhat + e0 + 4), rg1, rb1);
       }
       const float mean =
           half_sum((z0.x + z0.y + z0.z + z0.w) + (z1.x + z1.y + z1.z + z1.w)) * (1.f / 256);
@@ -135,9 +154,11 @@ FS2_DEV void nt_epilogue_ln(const GldsArgs& a, f32x4 (&acc)[BM / 32][256 / WN / 
                         (1.f / 256);
       const float rs = 1.f / sqrtf(var + 1e-5f);
       const f32x4 xh0 = c0 * rs, xh1 = c1 * rs;
-      const f32x4 u0 = xh0 * ga0 + be0, u1 = xh1 * ga1 + be1;
-      st4(a.ln_out + e0, u0);
-      st4(a.ln_out + e0 + 4, u1);
+      const f32x4 u0 = ln_affine(xh0, ga0, be0), u1 = ln_affine(xh1, ga1, be1);
+      if (a.ln_out) {
+        st4(a.ln_out + e0, u0);
+        st4(a.ln_out + e0 + 4, u1);
+      }
       if (a.ln_out_t) st8_bf16(a.ln_out_t + e0, u0, u1);
       st4(a.ln_xhat + e0, xh0);
       st4(a.ln_xhat + e0 + 4, xh1);
@@ -263,7 +284,7 @@ FS2_DEV void nt_epilogue(const GldsArgs& a, f32x4 (&acc)[BM / WM / 16][BN / WN /
   static_assert(WM % 2 == 0 && (SROW == 0 || MI % SROW == 0), "epilogue layout");
   constexpr int EPI_LD = BN + 4;
   if constexpr (BN == 256 && !VOC && WM == 2 && SROW == 0) {
-    if (a.ln_out) {
+    if (a.ln_xhat) {
       if constexpr (BM == 64) {
         if (a.ln_mode == 1) {
           nt_epilogue_lnbwd<BM, NWAVE, WN>(a, acc, smem, m0, tid, wm, wn, g, r16);

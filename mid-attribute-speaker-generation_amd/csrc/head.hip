@@ -191,22 +191,20 @@ Vp unpack_vp(const int64_t* w) {
   return v;
 }
 
-// forward region: h1 (fp32, the ReLU mask), u1 (fp32 LN output, unused downstream but written
-// by the LN kernel) + copy, xhat1, rstd1, h2, xhat2, rstd2, the LN2 output (written, unused),
-// pred
+// forward region: h1 (fp32, the ReLU mask), the bf16 copy of the LN1 output, xhat1, rstd1, h2,
+// xhat2, rstd2, pred.  Neither LayerNorm's fp32 output is stored: conv1d_2 reads the copy and
+// the Linear(., 1) runs inside the LN2 kernel.
 struct VpAct {
-  int64_t h1, u1, u1_t, xh1, rs1, h2, u2, xh2, rs2, pred, total;
+  int64_t h1, u1_t, xh1, rs1, h2, xh2, rs2, pred, total;
 };
 VpAct vp_act(const Vp& v, int64_t rows) {
   VpAct A;
   Take take;
   A.h1 = take(rows * v.filt * 4);
-  A.u1 = take(rows * v.filt * 4);
   A.u1_t = take(rows * v.filt * 2);
   A.xh1 = take(rows * v.filt * 4);
   A.rs1 = take(rows * 4);
   A.h2 = take(rows * v.filt * 4);
-  A.u2 = take(rows * v.filt * 4);
   A.xh2 = take(rows * v.filt * 4);
   A.rs2 = take(rows * 4);
   A.pred = take(rows * 4);
@@ -418,14 +416,14 @@ int fs2_variance_predictor_fwd(const int64_t* vp, const void* x_t, void* act, in
   FS2_TRY(fs2_conv_gemm(FS2_BF16, x_t, v.d, v.w1_f, h1, v.filt, rows, T, v.d, v.filt, (int)v.taps,
                         (int)v.pad1, nullptr, v.b1, FS2_EPI_BIAS | FS2_EPI_RELU, nullptr, v.filt,
                         stream));
-  FS2_TRY(fs2_ln_fwd(FS2_BF16, h1, nullptr, v.ln1_g, v.ln1_b, at<float>(act, A.u1), u1_t,
+  FS2_TRY(fs2_ln_fwd(FS2_BF16, h1, nullptr, v.ln1_g, v.ln1_b, nullptr, u1_t,
                      at<float>(act, A.xh1), at<float>(act, A.rs1), nullptr, 1, rows, (int)v.filt, 0.f,
                      p, sd, 0, (uint64_t)v.site, nullptr, nullptr, nullptr, stream));
   // Conv1d (padding 1, modules.py:230) -> ReLU -> LN -> dropout -> Linear(., 1), masked
   FS2_TRY(fs2_conv_gemm(FS2_BF16, u1_t, v.filt, v.w2_f, h2, v.filt, rows, T, v.filt, v.filt,
                         (int)v.taps, (int)v.pad2, nullptr, v.b2, FS2_EPI_BIAS | FS2_EPI_RELU, nullptr,
                         v.filt, stream));
-  return fs2_ln_fwd(FS2_F32, h2, nullptr, v.ln2_g, v.ln2_b, at<float>(act, A.u2), nullptr,
+  return fs2_ln_fwd(FS2_F32, h2, nullptr, v.ln2_g, v.ln2_b, nullptr, nullptr,
                     at<float>(act, A.xh2), at<float>(act, A.rs2), lens, T, rows, (int)v.filt, 0.f, p,
                     sd, 0, (uint64_t)(v.site + 1), v.lin_w, v.lin_b, at<float>(act, A.pred), stream);
 }

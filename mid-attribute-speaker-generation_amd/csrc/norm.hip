@@ -39,6 +39,11 @@ struct LnFwd {
   const float* dot_b;
   float* dot_out;
   unsigned short* out_t;  // optional bf16 copy of out
+  // the residual as the LayerNorm that produced it (res NULL): xhat * gamma + beta on the rows
+  // lens keeps, 0 on the masked ones (their xhat was never written and is not read)
+  const float* res_xhat;
+  const float* res_gamma;
+  const float* res_beta;
 };
 
 FS2_DEV bool row_padded(const int64_t* lens, int64_t T, int64_t r) {
@@ -54,14 +59,23 @@ __global__ __launch_bounds__(256) void ln_fwd_f32(LnFwd a) {
   const uint64_t seed = a.seed ? *a.seed : 0ull;
   const f32x4 ga0 = ld4(a.gamma + 8 * hl), ga1 = ld4(a.gamma + 8 * hl + 4);
   const f32x4 be0 = ld4(a.beta + 8 * hl), be1 = ld4(a.beta + 8 * hl + 4);
+  f32x4 rg0 = f32x4{0.f, 0.f, 0.f, 0.f}, rg1 = rg0, rb0 = rg0, rb1 = rg0;
+  if (a.res_xhat) {
+    rg0 = ld4(a.res_gamma + 8 * hl);
+    rg1 = ld4(a.res_gamma + 8 * hl + 4);
+    rb0 = ld4(a.res_beta + 8 * hl);
+    rb1 = ld4(a.res_beta + 8 * hl + 4);
+  }
   for (int64_t r = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5); r < a.rows;
        r += (int64_t)gridDim.x * 8) {
   const int64_t e0 = r * LN_D + 8 * hl;
   const bool pad = row_padded(a.lens, a.T, r);
   if (pad && !a.dot_out) {  // masked row: output 0; xhat/rstd are never read (bwd skips it)
     const f32x4 zz = {0.f, 0.f, 0.f, 0.f};
-    st4(a.out + e0, zz);
-    st4(a.out + e0 + 4, zz);
+    if (a.out) {
+      st4(a.out + e0, zz);
+      st4(a.out + e0 + 4, zz);
+    }
     if (a.out_t) st8_bf16(a.out_t + e0, zz, zz);
     continue;
   }
@@ -75,6 +89,9 @@ __global__ __launch_bounds__(256) void ln_fwd_f32(LnFwd a) {
   if (a.res) {
     z0 += ld4(a.res + e0);
     z1 += ld4(a.res + e0 + 4);
+  } else if (a.res_xhat && !pad) {  // (dot mode computes its masked rows: residual 0 there)
+    z0 += ln_affine(ld4(a.res_xhat + e0), rg0, rb0);
+    z1 += ln_affine(ld4(a.res_xhat + e0 + 4), rg1, rb1);
   }
   const float mean = half_sum((z0.x + z0.y + z0.z + z0.w) + (z1.x + z1.y + z1.z + z1.w)) * (1.f / LN_D);
   const f32x4 c0 = z0 - mean, c1 = z1 - mean;
@@ -82,16 +99,18 @@ __global__ __launch_bounds__(256) void ln_fwd_f32(LnFwd a) {
                              (c1.x * c1.x + c1.y * c1.y + c1.z * c1.z + c1.w * c1.w)) * (1.f / LN_D);
   const float rs = 1.f / sqrtf(var + 1e-5f);
   const f32x4 xh0 = c0 * rs, xh1 = c1 * rs;
-  f32x4 u0 = xh0 * ga0 + be0;
-  f32x4 u1 = xh1 * ga1 + be1;
+  f32x4 u0 = ln_affine(xh0, ga0, be0);
+  f32x4 u1 = ln_affine(xh1, ga1, be1);
   if (a.p_out > 0.f) {
     f32x4 m0, m1;
     dropout8(seed, a.site_out, (uint64_t)e0, a.p_out, m0, m1);
     u0 *= m0;
     u1 *= m1;
   }
-  st4(a.out + e0, u0);  // (dot mode masks only the head output)
-  st4(a.out + e0 + 4, u1);
+  if (a.out) {  // (dot mode masks only the head output)
+    st4(a.out + e0, u0);
+    st4(a.out + e0 + 4, u1);
+  }
   if (a.out_t) st8_bf16(a.out_t + e0, u0, u1);
   st4(a.xhat + e0, xh0);
   st4(a.xhat + e0 + 4, xh1);
@@ -651,14 +670,28 @@ int fs2_ln_fwd(int dtype, const float* y, const float* res, const float* gamma, 
                const uint64_t* seed, uint64_t site_in, uint64_t site_out, const float* dot_w,
                const float* dot_b,
                float* dot_out, void* stream) {
+  return fs2_ln_fwd_nres(dtype, y, res, nullptr, nullptr, nullptr, gamma, beta, out, out_t, xhat,
+                         rstd, lens, seq_len, rows, d, p_in, p_out, seed, site_in, site_out, dot_w,
+                         dot_b, dot_out, stream);
+}
+
+int fs2_ln_fwd_nres(int dtype, const float* y, const float* res, const float* res_xhat,
+                    const float* res_gamma, const float* res_beta, const float* gamma,
+                    const float* beta, float* out, void* out_t, float* xhat, float* rstd,
+                    const int64_t* lens, int64_t seq_len, int64_t rows, int d, float p_in,
+                    float p_out, const uint64_t* seed, uint64_t site_in, uint64_t site_out,
+                    const float* dot_w, const float* dot_b, float* dot_out, void* stream) {
   if (int rc = copy_dtype_ok(dtype, "fs2_ln_fwd")) return rc;
   FS2_CHECK_ARG(d == LN_D, "fs2_ln_fwd: only d = 256 is supported (got %d)", d);
   FS2_CHECK_ARG(!lens || seq_len > 0, "fs2_ln_fwd: lens given without seq_len");
   FS2_CHECK_ARG(!dot_out || (dot_w && dot_b), "fs2_ln_fwd: dot_out needs dot_w/dot_b");
+  FS2_CHECK_ARG(!res_xhat || (!res && res_gamma && res_beta),
+                "fs2_ln_fwd: give res or (res_xhat, res_gamma, res_beta), not both");
   if (rows == 0) return FS2_OK;
+  FS2_CHECK_ARG(y && gamma && beta && xhat && rstd, "fs2_ln_fwd: missing LayerNorm tensors");
   LnFwd a{y, res, gamma, beta, out, xhat, rstd, lens, seq_len, rows, p_in, p_out, seed,
           site_in, site_out, dot_w, dot_b, dot_out,
-          dtype == FS2_BF16 ? (unsigned short*)out_t : nullptr};
+          dtype == FS2_BF16 ? (unsigned short*)out_t : nullptr, res_xhat, res_gamma, res_beta};
   int64_t nb = (rows + 7) / 8;
   if (nb > 2048) nb = 2048;  // 8 blocks per CU, grid-stride beyond
   ln_fwd_f32<<<(unsigned)nb, 256, 0, as_stream(stream)>>>(a);

@@ -93,21 +93,24 @@ def conv_gemm(x, wk, rows, seq_len, c_in, c_out, taps, pad, bias=None, flags=0, 
 
 
 def conv_gemm_ln(x, wk, rows, seq_len, c_in, c_out, taps, pad, gamma, beta, bias=None, res=None,
-                 lens=None, p_in=0.0, seed=0, site_in=0, copy=torch.bfloat16):
+                 lens=None, p_in=0.0, seed=0, site_in=0, copy=torch.bfloat16, res_ln=None,
+                 want_out=True):
     """bf16 conv/Linear with the post-LayerNorm fused in (fs2_conv_gemm_ln): returns
     ``ln_fwd(conv_gemm(x) + bias, res=res, p_in=...)``'s (out fp32, out compute copy, xhat,
-    rstd), bitwise, without the fp32 intermediate."""
-    _dev(x, wk, gamma, beta, bias, res, lens)
+    rstd), bitwise, without the fp32 intermediate.  ``res_ln`` / ``want_out``: as ``ln_fwd``."""
+    rx, rg, rb = res_ln if res_ln is not None else (None, None, None)
+    _dev(x, wk, gamma, beta, bias, res, lens, rx, rg, rb)
     if x.dtype != torch.bfloat16 or wk.dtype != torch.bfloat16:
         raise RuntimeError("conv_gemm_ln: bf16 operands only")
-    out = torch.empty(rows, c_out, dtype=torch.float32, device=x.device)
+    out = torch.empty(rows, c_out, dtype=torch.float32, device=x.device) if want_out else None
     out_t = _copy((rows, c_out), copy, x.device)
-    xhat = torch.empty_like(out)
+    xhat = torch.empty(rows, c_out, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     sd = seed_arg(seed, x.device) if p_in > 0 else None
-    lib.fs2_conv_gemm_ln(ptr(x), c_in, ptr(wk), rows, seq_len, c_in, c_out, taps, pad, ptr(lens),
-                         ptr(bias), ptr(res), ptr(gamma), ptr(beta), ptr(out), ptr(out_t),
-                         ptr(xhat), ptr(rstd), p_in, ptr(sd), site_in, stream())
+    lib.fs2_conv_gemm_ln_nres(ptr(x), c_in, ptr(wk), rows, seq_len, c_in, c_out, taps, pad,
+                              ptr(lens), ptr(bias), ptr(res), ptr(rx), ptr(rg), ptr(rb),
+                              ptr(gamma), ptr(beta), ptr(out), ptr(out_t), ptr(xhat), ptr(rstd),
+                              p_in, ptr(sd), site_in, stream())
     return out, out_t, xhat, rstd
 
 
@@ -303,19 +306,24 @@ def attn_bwd(qkv, o, d_o, lse, lens, batch, seq_len, heads, d_head, scale):
 
 # ------------------------------------------------------------------ LayerNorm
 def ln_fwd(y, gamma, beta, res=None, lens=None, seq_len=1, p_in=0.0, p_out=0.0, seed=0,
-           site_in=0, site_out=0, dot_w=None, dot_b=None, copy=None):
-    """Returns (out fp32, out compute copy or None, xhat, rstd, dot)."""
-    _dev(y, gamma, beta, res, lens, dot_w, dot_b)
+           site_in=0, site_out=0, dot_w=None, dot_b=None, copy=None, res_ln=None, want_out=True):
+    """Returns (out fp32, out compute copy or None, xhat, rstd, dot).  ``res_ln`` = (xhat,
+    gamma, beta) of the LayerNorm that produced the residual, masked by the same ``lens``,
+    instead of ``res`` (fs2_ln_fwd_nres: the residual is rebuilt, bitwise what that LayerNorm
+    wrote, and its masked rows are never read).  ``want_out=False``: no fp32 output (None)."""
+    rx, rg, rb = res_ln if res_ln is not None else (None, None, None)
+    _dev(y, gamma, beta, res, lens, dot_w, dot_b, rx, rg, rb)
     rows, d = y.shape
-    out = torch.empty_like(y)
+    out = torch.empty_like(y) if want_out else None
     out_t = _copy(y.shape, copy, y.device)
     xhat = torch.empty_like(y)
     rstd = torch.empty(rows, dtype=torch.float32, device=y.device)
     dot = torch.empty(rows, dtype=torch.float32, device=y.device) if dot_w is not None else None
     sd = seed_arg(seed, y.device) if (p_in > 0 or p_out > 0) else None
-    lib.fs2_ln_fwd(BF16 if copy is not None else F32, ptr(y), ptr(res), ptr(gamma), ptr(beta),
-                   ptr(out), ptr(out_t), ptr(xhat), ptr(rstd), ptr(lens), seq_len, rows, d, p_in,
-                   p_out, ptr(sd), site_in, site_out, ptr(dot_w), ptr(dot_b), ptr(dot), stream())
+    lib.fs2_ln_fwd_nres(BF16 if copy is not None else F32, ptr(y), ptr(res), ptr(rx), ptr(rg),
+                        ptr(rb), ptr(gamma), ptr(beta), ptr(out), ptr(out_t), ptr(xhat), ptr(rstd),
+                        ptr(lens), seq_len, rows, d, p_in, p_out, ptr(sd), site_in, site_out,
+                        ptr(dot_w), ptr(dot_b), ptr(dot), stream())
     return out, out_t, xhat, rstd, dot
 
 

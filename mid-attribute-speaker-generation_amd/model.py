@@ -446,9 +446,18 @@ class FFTBlock(nn.Module):
         self._cdesc = (key, arr)
         return arr
 
-    def fwd(self, x, x_t, lens, B, T, ctx):
+    def fwd(self, x, x_t, lens, B, T, ctx, prev_ln=None, want_x2=True):
+        """Block forward: (x2 fp32, its compute copy, saved).  With compute copies the fp32
+        residual stream between the post-LN sites is not stored: LN1's output is rebuilt from
+        its xhat by the w_2 site, and ``prev_ln`` = (xh2, gamma, beta) of the previous block's
+        LN2 stands for ``x`` (None) at the fc site (K.ln_fwd's ``res_ln``; bitwise the stored
+        value).  ``want_x2=False``: x2 is returned as None -- the next block takes this block's
+        ``ln2_res(saved)``, and the mel head reads only the copy."""
         a, f = self.slf_attn, self.pos_ffn
-        M, d = x.shape
+        M, d = (x if x is not None else x_t).shape
+        lean = ctx.copy is not None
+        want_x2 = want_x2 or not lean
+        res_in = dict(res=x) if prev_ln is None else dict(res_ln=prev_ln)
         q = self._qkv_holder
         n3 = q.out_features
         p = ctx.p(a.p)
@@ -466,13 +475,15 @@ class FFTBlock(nn.Module):
         if fuse:
             x1, x1_t, xh1, rs1 = K.conv_gemm_ln(
                 o, a.fc._w_fwd, M, T, hd, d, 1, 0, a.layer_norm.weight, a.layer_norm.bias,
-                bias=a.fc.bias, res=x, lens=lens, p_in=p, seed=ctx.seed, site_in=self.site,
-                copy=ctx.copy)
+                bias=a.fc.bias, lens=lens, p_in=p, seed=ctx.seed, site_in=self.site,
+                copy=ctx.copy, want_out=not lean, **res_in)
         else:
             y1 = K.conv_gemm(o, a.fc._w_fwd, M, T, hd, d, 1, 0, bias=a.fc.bias, lens=lens)
-            x1, x1_t, xh1, rs1, _ = K.ln_fwd(y1, a.layer_norm.weight, a.layer_norm.bias, res=x,
+            x1, x1_t, xh1, rs1, _ = K.ln_fwd(y1, a.layer_norm.weight, a.layer_norm.bias,
                                              lens=lens, seq_len=T, p_in=p, seed=ctx.seed,
-                                             site_in=self.site, copy=ctx.copy)
+                                             site_in=self.site, copy=ctx.copy, want_out=not lean,
+                                             **res_in)
+        res_1 = dict(res_ln=(xh1, a.layer_norm.weight, a.layer_norm.bias)) if lean else dict(res=x1)
         w1, w2 = f.w_1, f.w_2
         x1_c = _t(x1, x1_t)
         h = K.conv_gemm(x1_c, w1._w_fwd, M, T, d, w1.c_out, w1.k, w1.padding, bias=w1.bias,
@@ -480,16 +491,22 @@ class FFTBlock(nn.Module):
         if fuse:
             x2, x2_t, xh2, rs2 = K.conv_gemm_ln(
                 h, w2._w_fwd, M, T, w2.c_in, d, w2.k, w2.padding, f.layer_norm.weight,
-                f.layer_norm.bias, bias=w2.bias, res=x1, lens=lens, p_in=p, seed=ctx.seed,
-                site_in=self.site + 1, copy=ctx.copy)
+                f.layer_norm.bias, bias=w2.bias, lens=lens, p_in=p, seed=ctx.seed,
+                site_in=self.site + 1, copy=ctx.copy, want_out=want_x2, **res_1)
         else:
             y2 = K.conv_gemm(h, w2._w_fwd, M, T, w2.c_in, d, w2.k, w2.padding, bias=w2.bias,
                              lens=lens)
-            x2, x2_t, xh2, rs2, _ = K.ln_fwd(y2, f.layer_norm.weight, f.layer_norm.bias, res=x1,
+            x2, x2_t, xh2, rs2, _ = K.ln_fwd(y2, f.layer_norm.weight, f.layer_norm.bias,
                                              lens=lens, seq_len=T, p_in=p, seed=ctx.seed,
-                                             site_in=self.site + 1, copy=ctx.copy)
+                                             site_in=self.site + 1, copy=ctx.copy,
+                                             want_out=want_x2, **res_1)
         saved = (x_c, qkv, o, lse, x1_c, h, xh1, rs1, xh2, rs2, p, ctx, lens, B, T)
         return x2, x2_t, saved
+
+    def ln2_res(self, saved):
+        """This block's output as the next block's ``prev_ln``."""
+        ln2 = self.pos_ffn.layer_norm
+        return saved[8], ln2.weight, ln2.bias
 
     def bwd(self, dx2, saved, ln2_done=None, prev=None):
         """Block backward from the gradient of its output.  ``ln2_done`` = (dy2 copy, dx1):
@@ -568,35 +585,57 @@ def _c_blocks(ctx, d):
     return C_BLOCKS and ctx.copy is not None and ctx.cdt == torch.bfloat16 and d == 256
 
 
-def _stack_fwd_c(layers, x, x_t, lens, B, T, ctx, after_first=None):
-    """Forward through a stack of FFT blocks, one fs2_fft_block_fwd call per block; each block's
-    activations live in one region (saved for the backward); ``after_first`` is called once the
-    first block is issued.  Returns the last block's output, its bf16 copy and the per-block
-    saved tuples."""
+def _stack_fwd(layers, x, x_t, lens, B, T, ctx, keep_x2, after_first=None):
+    """Forward through a stack of FFT blocks, one kernel call at a time.  With compute copies
+    only the last block stores its fp32 output, and only with ``keep_x2`` (a reader outside the
+    stack): each inner block hands the next one its LN2 (FFTBlock.fwd).  Returns the last
+    block's output (None when not stored), its compute copy and the per-block saved tuples."""
+    saved, prev_ln = [], None
+    for i, layer in enumerate(layers):
+        last = i + 1 == len(layers)
+        x, x_t, s = layer.fwd(x, x_t, lens, B, T, ctx, prev_ln=prev_ln,
+                              want_x2=keep_x2 if last else False)
+        prev_ln = layer.ln2_res(s) if x is None else None
+        saved.append(s)
+        if after_first is not None:
+            after_first()
+            after_first = None
+    return x, x_t, saved
+
+
+def _stack_fwd_c(layers, x, x_t, lens, B, T, ctx, keep_x2, after_first=None):
+    """Forward through a stack of FFT blocks, one fs2_fft_block_fwd_nres call per block; each
+    block's activations live in one region (saved for the backward); ``after_first`` is called
+    once the first block is issued.  Only the last block stores its fp32 output, and only with
+    ``keep_x2``; the others hand the next block their region.  Returns the last block's output
+    (None when not stored), its bf16 copy and the per-block saved tuples."""
     M, d = x.shape
     fuse = FUSE_LN and M >= FUSE_LN_MIN_ROWS
     saved = []
     xp, xtp, x_keep = x.data_ptr(), x_t.data_ptr(), x_t
     lp = 0 if lens is None else lens.data_ptr()
     stream = K.stream()
-    acts = []
-    for layer in layers:
+    pdesc, pact = None, None
+    for i, layer in enumerate(layers):
         desc = layer.cdesc()
         p = ctx.p(layer.slf_attn.p)
-        act = _region(_csize('fs2_fft_block_act_bytes', desc, 7, M, B, T, int(fuse)), x.device,
-                      "fft_block act")
-        K.lib.fs2_fft_block_fwd(desc, xp, xtp, act.data_ptr(), M, B, T, lp, p,
-                                ctx.seed.data_ptr() if p > 0 else None, int(fuse), stream)
+        x2 = int(keep_x2 and i + 1 == len(layers))
+        act = _region(_csize('fs2_fft_block_act_bytes_x2', desc, 7, M, B, T, int(fuse), x2),
+                      x.device, "fft_block act")
+        K.lib.fs2_fft_block_fwd_nres(desc, xp, xtp, pdesc, pact, int(fuse), x2, act.data_ptr(), M,
+                                     B, T, lp, p, ctx.seed.data_ptr() if p > 0 else None,
+                                     int(fuse), stream)
         if after_first is not None:
             after_first()
             after_first = None
         saved.append(("C", act, xtp, x_keep, fuse, p))
-        o2 = _csize('fs2_fft_block_act_offset', desc, 7, M, B, T, int(fuse), 0)
-        o2t = _csize('fs2_fft_block_act_offset', desc, 7, M, B, T, int(fuse), 1)
-        xp, xtp, x_keep = act.data_ptr() + o2, act.data_ptr() + o2t, act
-        acts.append((act, o2, o2t))
-    act, o2, o2t = acts[-1]
-    out = act[o2:o2 + M * d * 4].view(torch.float32).view(M, d)
+        o2t = _csize('fs2_fft_block_act_offset_x2', desc, 7, M, B, T, int(fuse), x2, 1)
+        xp, xtp, x_keep = None, act.data_ptr() + o2t, act
+        pdesc, pact = desc, act.data_ptr()
+    out = None
+    if x2:
+        o2 = _csize('fs2_fft_block_act_offset_x2', desc, 7, M, B, T, int(fuse), x2, 0)
+        out = act[o2:o2 + M * d * 4].view(torch.float32).view(M, d)
     out_t = act[o2t:o2t + M * d * 2].view(torch.bfloat16).view(M, d)
     return out, out_t, saved
 
@@ -762,14 +801,15 @@ class VariancePredictor(nn.Module):
         h1 = K.conv_gemm(x_c, c1._w_fwd, M, T, c1.c_in, c1.c_out, c1.k, c1.padding, bias=c1.bias,
                          flags=K.EPI_RELU)
         u1, u1_t, xh1, rs1, _ = K.ln_fwd(h1, c.layer_norm_1.weight, c.layer_norm_1.bias, p_out=p,
-                                         seed=ctx.seed, site_out=self.site, copy=ctx.copy)
+                                         seed=ctx.seed, site_out=self.site, copy=ctx.copy,
+                                         want_out=ctx.copy is None)
         u1_c = _t(u1, u1_t)
         h2 = K.conv_gemm(u1_c, c2._w_fwd, M, T, c2.c_in, c2.c_out, c2.k, c2.padding, bias=c2.bias,
                          flags=K.EPI_RELU)
         _, _, xh2, rs2, pred = K.ln_fwd(h2, c.layer_norm_2.weight, c.layer_norm_2.bias, lens=lens,
                                         seq_len=T, p_out=p, seed=ctx.seed, site_out=self.site + 1,
                                         dot_w=self.linear_layer.weight,
-                                        dot_b=self.linear_layer.bias)
+                                        dot_b=self.linear_layer.bias, want_out=False)
         saved = (x_c, h1, u1_c, h2, xh1, rs1, xh2, rs2, p, ctx, lens, T)
         return pred.view(B, T), saved
 
@@ -1112,15 +1152,10 @@ class EncoderFn(torch.autograd.Function):
                                  enc.position_enc, B, T, enc.d, copy=ctx.copy)
         after_first, ctx.after_first = ctx.after_first, None
         if _c_blocks(ctx, enc.d) and x_t is not None:
-            x, x_t, saved = _stack_fwd_c(enc.layer_stack, x, x_t, lens, B, T, ctx, after_first)
+            x, x_t, saved = _stack_fwd_c(enc.layer_stack, x, x_t, lens, B, T, ctx, True,
+                                         after_first)
         else:
-            saved = []
-            for layer in enc.layer_stack:
-                x, x_t, s = layer.fwd(x, x_t, lens, B, T, ctx)
-                saved.append(s)
-                if after_first is not None:
-                    after_first()
-                    after_first = None
+            x, x_t, saved = _stack_fwd(enc.layer_stack, x, x_t, lens, B, T, ctx, True, after_first)
         if not enc.layer_stack and after_first is not None:
             after_first()
         fctx.enc, fctx.saved, fctx.ids, fctx.ctx = enc, saved, (texts, accents), ctx
@@ -1338,13 +1373,15 @@ class DecoderFn(torch.autograd.Function):
     def forward(fctx, token, x, x_t, dec, lens, B, T, ctx):
         fctx.set_materialize_grads(False)  # the compute-copy side output gets no zero gradient
         x_t = x_t if x_t.numel() else None
+        shape, dev = tuple(x.shape), x.device
         if _c_blocks(ctx, x.shape[1]) and x_t is not None:
-            x, x_t, saved = _stack_fwd_c(dec.layer_stack, x, x_t, lens, B, T, ctx)
+            x, x_t, saved = _stack_fwd_c(dec.layer_stack, x, x_t, lens, B, T, ctx, False)
         else:
-            saved = []
-            for layer in dec.layer_stack:
-                x, x_t, s = layer.fwd(x, x_t, lens, B, T, ctx)
-                saved.append(s)
+            x, x_t, saved = _stack_fwd(dec.layer_stack, x, x_t, lens, B, T, ctx, False)
+        if x is None:
+            # the mel head reads the compute copy only: the fp32 output is not stored, and a
+            # storage-free tensor of its shape carries the gradient through autograd
+            x = torch.empty(1, dtype=torch.float32, device=dev).expand(shape)
         fctx.dec, fctx.saved, fctx.ctx = dec, saved, ctx
         fctx.geom, fctx.xshape, fctx.xdev = (lens, B, T), tuple(x.shape), x.device
         side = x_t if x_t is not None else torch.empty(0, device=x.device)
@@ -1748,8 +1785,7 @@ class FastSpeech2(nn.Module):
             x, x_t = K.encoder_embed(texts.contiguous(), accents.contiguous(),
                                      enc.src_word_emb.weight, enc.src_accent_emb.weight,
                                      enc.position_enc, B, Ts, enc.d, copy=ctx.copy)
-            for layer in enc.layer_stack:
-                x, x_t, _ = layer.fwd(x, x_t, src_lens, B, Ts, ctx)
+            x, x_t, _ = _stack_fwd(enc.layer_stack, x, x_t, src_lens, B, Ts, ctx, True)
             if speaker_vec is None:
                 ids, table = speakers.contiguous(), self.speaker_emb.weight
                 speaker_emb_s = K.embedding_fwd(ids, table)
@@ -1807,8 +1843,7 @@ class FastSpeech2(nn.Module):
                                                        p_targets, e_targets, values, ctx)
             else:
                 x, x_t = K.lr_expand(x2, cum, T_dec, posenc=self._posenc(T_dec), copy=ctx.copy)
-            for layer in dec.layer_stack:
-                x, x_t, _ = layer.fwd(x, x_t, dec_lens, B, T_dec, ctx)
+            x, x_t, _ = _stack_fwd(dec.layer_stack, x, x_t, dec_lens, B, T_dec, ctx, False)
             lin = self.mel_linear
             M = B * T_dec
             out = K.conv_gemm(_t(x, x_t), lin._w_fwd, M, T_dec, lin.in_features,
