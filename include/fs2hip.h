@@ -1399,6 +1399,60 @@ int fs2_path_metrics(const double* cost, const int* path, const int* path_len, c
                      const int64_t* lb, int64_t batch, int64_t t1_max, int64_t t2_max,
                      const float* fa, const float* fb, double* rec, void* stream);
 
+/* ---------------------------------------------------------------- alignment without TextGrids
+ * Not in the reference (its corpora come aligned by the Montreal Forced Aligner; its jdit branch,
+ * model/jdit.py, is not ported): the hot path of the alignment learning framework (Badlani et
+ * al. 2021) -- csrc/align.hip; DESIGN.md §7.  All tensors fp32; src_lens / mel_lens are device
+ * int64[B], never read back, N = src_lens[b] clamped into 1..T_s and M = mel_lens[b] into
+ * 1..T_m.  A row's result does not depend on its place in the batch; no atomics, every
+ * reduction in a fixed order.  batch = 0 launches nothing.  T_s <= FS2_ALIGN_MAX_SRC, T_m <=
+ * FS2_ALIGN_MAX_MEL, attention width A <= FS2_ALIGN_MAX_WIDTH with A % 8 == 0.
+ *
+ * fs2_align_logprob: q (B, T_m, A), k (B, T_s, A) -> logp (B, T_m, T_s); for t < M, s < N
+ *   logp[t, s] = log_softmax_{s < N}(-temperature |q_t - k_s|^2) + prior(t, s),
+ * prior = 0 when omega <= 0, else the log beta-binomial pmf of s with n = N - 1,
+ * a = omega (t + 1), b = omega (M - t), formed with fp64 lgamma, rounded once and added to the
+ * fp32 log-softmax (never stored on its own).  Cells with t >= M or s >= N are written as 0.
+ *
+ * fs2_align_logprob_bwd: g = dL/dlogp (B, T_m, T_s), cells with t >= M or s >= N not read ->
+ * dq (B, T_m, A), dk (B, T_s, A), zero in dead rows.  The softmax is recomputed from q and k.
+ * dk is summed over frames in a fixed order: partials of 256 frames, each in frame order, then
+ * the partials in order.  The workspace holds dL/dscore and the partials.
+ *
+ * fs2_forward_sum: one workgroup per utterance.  For each frame t < M the N + 1 scores
+ * [blank = -1, logp[t, 0..N-1]] are log-softmaxed and the CTC recursion runs over the 2N + 1
+ * states of the target 1, 2, .., N (distinct labels: the skip transition is always open), alpha
+ * and beta in fp64 in the log domain.  nll[b] = -log p(target); grad (B, T_m, T_s) =
+ * d(nll[b] w[b]) / dlogp with caller-supplied weights w (B), dead cells 0.  The workspace holds
+ * the label states' alpha; beta is combined with it on the fly.  M < N has no valid path:
+ * nll[b] = +inf and grad = 0 for that row.
+ *
+ * fs2_mas: monotonic alignment search, one workgroup per utterance.  fp32, one add per cell:
+ *   V[0, 0] = logp[0, 0], V[0, s > 0] = -inf, V[t, s] = logp[t, s] + max(V[t-1, s-1], V[t-1, s])
+ * with the diagonal s - 1 taken on a tie (V[t-1, -1] = -inf); the path ends at (M-1, N-1) and is
+ * traced back in the same launch from one step byte per cell in the workspace.  durations
+ * (B, T_s) int64 = frames per phoneme, >= 1 for s < N, 0 for s >= N.  A row with M < N has no
+ * such path: its durations are all 0 (callers that know the lengths reject it beforehand).   */
+#define FS2_ALIGN_MAX_SRC 1024
+#define FS2_ALIGN_MAX_MEL 2048
+#define FS2_ALIGN_MAX_WIDTH 128
+int fs2_align_logprob(const float* q, const float* k, const int64_t* src_lens,
+                      const int64_t* mel_lens, int64_t batch, int64_t t_m, int64_t t_s, int64_t a,
+                      float temperature, float omega, float* logp, void* stream);
+int64_t fs2_align_logprob_bwd_ws_bytes(int64_t batch, int64_t t_m, int64_t t_s, int64_t a);
+int fs2_align_logprob_bwd(const float* q, const float* k, const float* g, const int64_t* src_lens,
+                          const int64_t* mel_lens, int64_t batch, int64_t t_m, int64_t t_s,
+                          int64_t a, float temperature, float* dq, float* dk, void* ws,
+                          int64_t ws_bytes, void* stream);
+int64_t fs2_forward_sum_ws_bytes(int64_t batch, int64_t t_m, int64_t t_s);
+int fs2_forward_sum(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
+                    const float* w, int64_t batch, int64_t t_m, int64_t t_s, float* nll,
+                    float* grad, void* ws, int64_t ws_bytes, void* stream);
+int64_t fs2_mas_ws_bytes(int64_t batch, int64_t t_m, int64_t t_s);
+int fs2_mas(const float* logp, const int64_t* src_lens, const int64_t* mel_lens, int64_t batch,
+            int64_t t_m, int64_t t_s, int64_t* durations, void* ws, int64_t ws_bytes,
+            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
   read_wav        what ``librosa.load(path, sr=None, mono=True)`` decodes (preprocessor.py:186;
                   the resampling that call also does is ``audio.Resampler``, on the device)
   read_textgrid   what ``tgt.io.read_textgrid`` reads (preprocessor.py:177), as plain tuples
+  write_textgrid  one interval tier from frame durations (``align.py``), read back exactly
 """
 import re
 import struct
@@ -119,3 +120,41 @@ def read_textgrid(path, include_empty_intervals=False):
         return tiers
     except (IndexError, ValueError, TypeError):
         raise ValueError(f"{path}: not a TextGrid this reader understands") from None
+
+
+def boundary_time(n_frames, hop, sr):
+    """The time written for a boundary after ``n_frames`` frames: half a sample past
+    ``n_frames * hop / sr``.  The plain quotient does not survive the trip through its decimal
+    text and ``int(sr * t)``: for hop 256 at 22 050 Hz, 326 of the boundaries 1..3999 come back one
+    sample short, which leaves the trimmed waveform one frame short of its durations.  With the
+    half sample ``int(sr * t)`` is ``n_frames * hop`` and ``round(t * sr / hop)`` is ``n_frames``
+    whatever way the last bit rounds."""
+    return (int(n_frames) * int(hop) + 0.5) / float(sr)
+
+
+def write_textgrid(path, phones, durations, hop, sr, tier="phones"):
+    """Write a long-format TextGrid with one interval tier: phone ``i`` lasts ``durations[i]``
+    frames of ``hop`` samples at ``sr``, boundaries at ``boundary_time``.  ``read_textgrid``,
+    ``preprocess.durations_from_intervals`` and the trim ``int(sr * start):int(sr * end)`` give
+    back these durations and a waveform of ``sum(durations) * hop`` samples (leading and trailing
+    silence phones are trimmed there as for any TextGrid)."""
+    phones, durations = list(phones), [int(d) for d in durations]
+    if len(phones) != len(durations) or not phones:
+        raise ValueError(f"{path}: {len(phones)} phones and {len(durations)} durations")
+    if any(d < 0 for d in durations) or any(str(p).strip() == "" for p in phones):
+        raise ValueError(f"{path}: a negative duration or an empty phone")
+    edges = [0]
+    for d in durations:
+        edges.append(edges[-1] + d)
+    times = [repr(boundary_time(n, hop, sr)) for n in edges]
+    lines = ['File type = "ooTextFile"', 'Object class = "TextGrid"', "", "xmin = 0",
+             f"xmax = {times[-1]}", "tiers? <exists>", "size = 1", "item []:", "    item [1]:",
+             '        class = "IntervalTier"', '        name = "' + tier.replace('"', '""') + '"',
+             "        xmin = 0", f"        xmax = {times[-1]}",
+             f"        intervals: size = {len(phones)}"]
+    for i, p in enumerate(phones):
+        lines += [f"        intervals [{i + 1}]:", f"            xmin = {times[i]}",
+                  f"            xmax = {times[i + 1]}",
+                  '            text = "' + str(p).replace('"', '""') + '"']
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\n".join(lines) + "\n")

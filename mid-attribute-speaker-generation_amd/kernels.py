@@ -1668,3 +1668,97 @@ def path_metrics(cost, path, path_len, la, lb, t1_max, t2_max, fa=None, fb=None)
     lib.fs2_path_metrics(ptr(cost), ptr(path), ptr(path_len), ptr(la), ptr(lb), B, T1, T2, ptr(fa),
                          ptr(fb), ptr(rec), stream())
     return rec
+
+
+# ------------------------------------------------------------------ alignment without TextGrids
+ALIGN_MAX_SRC = 1024   # FS2_ALIGN_MAX_SRC
+ALIGN_MAX_MEL = 2048   # FS2_ALIGN_MAX_MEL
+ALIGN_MAX_WIDTH = 128  # FS2_ALIGN_MAX_WIDTH
+
+
+def _align_qk(name, q, k, src_lens, mel_lens):
+    _dev(q, k)
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or q.dim() != 3 or k.dim() != 3 or \
+            q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise RuntimeError(f"{name}: q (B, T_m, A) and k (B, T_s, A) are f32")
+    B, T_m, A = q.shape
+    _lens_i64(name, src_lens, B)
+    _lens_i64(name, mel_lens, B)
+    return B, T_m, k.shape[1], A
+
+
+def _align_logp(name, logp, src_lens, mel_lens):
+    _dev(logp)
+    if logp.dtype != torch.float32 or logp.dim() != 3:
+        raise RuntimeError(f"{name}: logp (B, T_m, T_s) is f32")
+    B, T_m, T_s = logp.shape
+    _lens_i64(name, src_lens, B)
+    _lens_i64(name, mel_lens, B)
+    return B, T_m, T_s
+
+
+def _align_path_exists(name, host_lens):
+    """``host_lens``: (src, mel) length lists where the caller has them on the host."""
+    if host_lens is not None:
+        for b, (n, m) in enumerate(zip(*host_lens)):
+            if int(m) < int(n):
+                raise RuntimeError(f"{name}: row {b} has {int(m)} frames for {int(n)} phonemes "
+                                   "(no monotonic path)")
+
+
+def align_logprob(q, k, src_lens, mel_lens, temperature, omega=0.0):
+    """fs2_align_logprob: q (B, T_m, A), k (B, T_s, A) f32, device int64 lengths -> logp
+    (B, T_m, T_s) = log_softmax_s(-temperature |q_t - k_s|^2) + the log beta-binomial prior
+    (``omega`` <= 0: none); cells past a row's lengths are 0."""
+    B, T_m, T_s, A = _align_qk("align_logprob", q, k, src_lens, mel_lens)
+    logp = torch.empty((B, T_m, T_s), dtype=torch.float32, device=q.device)
+    lib.fs2_align_logprob(ptr(q), ptr(k), ptr(src_lens), ptr(mel_lens), B, T_m, T_s, A,
+                          float(temperature), float(omega), ptr(logp), stream())
+    return logp
+
+
+def align_logprob_bwd(q, k, g, src_lens, mel_lens, temperature):
+    """fs2_align_logprob_bwd: g = dL/dlogp (B, T_m, T_s) -> ``(dq, dk)``; the softmax is recomputed
+    and the prior has no gradient."""
+    B, T_m, T_s, A = _align_qk("align_logprob_bwd", q, k, src_lens, mel_lens)
+    _dev(g)
+    if g.dtype != torch.float32 or tuple(g.shape) != (B, T_m, T_s):
+        raise RuntimeError(f"align_logprob_bwd: g is f32 ({B}, {T_m}, {T_s})")
+    dq, dk = torch.empty_like(q), torch.empty_like(k)
+    nb = lib.fs2_align_logprob_bwd_ws_bytes(B, T_m, T_s, A)
+    wk = ws(nb, q.device)
+    lib.fs2_align_logprob_bwd(ptr(q), ptr(k), ptr(g), ptr(src_lens), ptr(mel_lens), B, T_m, T_s, A,
+                              float(temperature), ptr(dq), ptr(dk), ptr(wk), nb, stream())
+    return dq, dk
+
+
+def forward_sum(logp, src_lens, mel_lens, w, host_lens=None):
+    """fs2_forward_sum: the CTC forward-sum loss of the target 1..N under logp (blank score -1)
+    -> ``(nll (B) f32, grad (B, T_m, T_s) = d(nll[b] w[b]) / dlogp)``.  ``host_lens`` = (src, mel)
+    host lists: a row with fewer frames than phonemes raises before the launch (on the device
+    such a row gives nll = +inf and a zero gradient)."""
+    B, T_m, T_s = _align_logp("forward_sum", logp, src_lens, mel_lens)
+    _dev(w)
+    if w.dtype != torch.float32 or w.numel() != B:
+        raise RuntimeError(f"forward_sum: w is f32 ({B})")
+    _align_path_exists("forward_sum", host_lens)
+    nll = torch.empty(B, dtype=torch.float32, device=logp.device)
+    grad = torch.empty_like(logp)
+    nb = lib.fs2_forward_sum_ws_bytes(B, T_m, T_s)
+    wk = torch.empty(max(nb // 8, 1), dtype=torch.float64, device=logp.device)
+    lib.fs2_forward_sum(ptr(logp), ptr(src_lens), ptr(mel_lens), ptr(w), B, T_m, T_s, ptr(nll),
+                        ptr(grad), ptr(wk), nb, stream())
+    return nll, grad
+
+
+def mas(logp, src_lens, mel_lens, host_lens=None):
+    """fs2_mas: monotonic alignment search -> durations (B, T_s) int64, frames per phoneme (>= 1
+    below a row's phoneme count, 0 past it).  ``host_lens`` as in ``forward_sum``."""
+    B, T_m, T_s = _align_logp("mas", logp, src_lens, mel_lens)
+    _align_path_exists("mas", host_lens)
+    durations = torch.empty((B, T_s), dtype=torch.int64, device=logp.device)
+    nb = lib.fs2_mas_ws_bytes(B, T_m, T_s)
+    wk = torch.empty(max(nb, 1), dtype=torch.uint8, device=logp.device)
+    lib.fs2_mas(ptr(logp), ptr(src_lens), ptr(mel_lens), B, T_m, T_s, ptr(durations), ptr(wk), nb,
+                stream())
+    return durations
