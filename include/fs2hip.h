@@ -264,6 +264,23 @@ int64_t fs2_ge2e_softmax_ws_bytes(int64_t n_spk, int64_t m_utt, int64_t dim);
 int fs2_ge2e_softmax(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim, const float* w,
                      const float* b, const float* g, float* loss, float* demb, float* dw,
                      float* db, float* ws, int64_t ws_bytes, void* stream);
+/* GE2E contrast loss (hp.model.loss == 'contrast'; utils.py:77-90, 106-124,
+ * speech_embedder_net.py:173-179) on the same operands, limits and nullability as
+ * fs2_ge2e_softmax.  S_jik as there (w cos + b, each norm clamped at 1e-8, the k = j entry
+ * against the exclude-self centroid (sum_i e_ji - e_ji) / (m_utt - 1)), sig = 1 / (1 + exp(-S)),
+ *   loss = sum_ji (1 - sig(S_jij)) + sum_ji max_k sig~_jik,
+ * sig~_jik = sig(S_jik) for k != j and sig~_jij = 0: the reference zeroes the own-speaker entry
+ * in place, so it takes part in the maximum with value 0 and carries no gradient (n_spk = 1:
+ * the second sum is 0).  Equal values: the lowest k wins, the index torch.max(dim=2) reports.
+ * Gradients: dL/dS_jij = -sig (1 - sig), dL/dS_jik* = +sig (1 - sig) at the winning k*, nothing
+ * else; dw = g sum dS cos, db = g sum dS, demb through the cosine into e_ji, the winning
+ * centroid's m_utt members and the exclude-self centroid's m_utt - 1 members.  One workgroup,
+ * fixed-order reductions, bitwise repeatable.  ws: fs2_ge2e_contrast_ws_bytes (0 on a bad
+ * shape).                                                                                 */
+int64_t fs2_ge2e_contrast_ws_bytes(int64_t n_spk, int64_t m_utt, int64_t dim);
+int fs2_ge2e_contrast(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim, const float* w,
+                      const float* b, const float* g, float* loss, float* demb, float* dw,
+                      float* db, float* ws, int64_t ws_bytes, void* stream);
 /* Speaker-encoder batches cut on the device (data_load.py:107-110, 122-129):
  *   out[r, t, c] = store[row_off[r] + c * row_stride[r] + row_start[r] + t],  t < len, c < n_mels.
  * A row's source is one utterance stored (n_mels, frames) inside the flat corpus `store`:

@@ -1,8 +1,9 @@
 // Training the GE2E speaker encoder (train_speech_embedder.py): what the --use_clf path of
 // train.py never needs -- the head's weight gradients, the GE2E softmax loss for M > 1
-// utterances per speaker (utils.py:77-90, 126-135, speech_embedder_net.py:173-181), and Adam
-// with torch.optim.Adam's coupled L2 weight decay.  The LSTM weight gradients are in
-// lstm_wgrad.hip.  fp32 throughout; every reduction runs in a fixed order (no atomics).
+// utterances per speaker (utils.py:77-90, 126-135, speech_embedder_net.py:173-181) and its
+// 'contrast' alternative (utils.py:106-124), and Adam with torch.optim.Adam's coupled L2 weight
+// decay.  The LSTM weight gradients are in lstm_wgrad.hip.  fp32 throughout; every reduction
+// runs in a fixed order (no atomics).
 #include <math.h>
 
 #include "common.hpp"
@@ -303,6 +304,159 @@ __global__ __launch_bounds__(64 * GE_WAVES) void ge2e_softmax_kernel(Ge2e a) {
   }
 }
 
+// ---------------------------------------------------------------- GE2E contrast loss
+// hp.model.loss == 'contrast' (utils.py:106-124) on the S of the softmax kernel above:
+//   sig = 1 / (1 + exp(-S)),   loss = sum_ji (1 - sig(S_jij)) + max_k sig~_jik,
+// sig~_jik = sig(S_jik) for k != j and sig~_jij = 0 -- the reference zeroes the own-speaker entry
+// in place, so it takes part in the maximum with value 0 and carries no gradient.  The scan over
+// k keeps the first strict maximum: on equal values the lowest k wins, as torch.max(dim=2).
+//   dL/dS_jij = -sig (1 - sig),  dL/dS_jik* = +sig (1 - sig) at the winner k*,  nothing else.
+// 1 - sig is formed as 1 / (1 + exp(S)): the subtraction would keep 6e-8 absolute of a value
+// that is 7e-3 at S = 5.
+// Same block shape and phases as ge2e_softmax_kernel; a row has at most two centroid terms, so
+// phase B leaves per row the winner's index and its two coefficients (no (NM, N) tables) and
+// the gradient into its exclude-self centroid; phase C gathers each centroid's rows in row order.
+__global__ __launch_bounds__(64 * GE_WAVES) void ge2e_contrast_kernel(Ge2e a) {
+  __shared__ float red[GE_WAVES][3];
+  const int N = a.N, M = a.M, D = a.D, NM = N * M;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  float* csum = a.ws;                             // (N, D)
+  float* cmean = csum + N * D;                    // (N, D)
+  float* cnrm = cmean + N * D;                    // (N)
+  int* kwin = reinterpret_cast<int*>(cnrm + N);   // (NM) winning k, -1: no gradient
+  float* coefA = cnrm + N + NM;                   // (NM)
+  float* coefB = coefA + NM;                      // (NM)
+  float* dcx = coefB + NM;                        // (NM, D)
+  float* dc = dcx + NM * D;                       // (N, D)
+  const bool grads = a.demb != nullptr;
+  const float w = a.w[0], b = a.b[0], g = a.g ? a.g[0] : 1.f;
+  const float inv_m1 = 1.f / (float)(M - 1);
+
+  for (int idx = tid; idx < N * D; idx += blockDim.x) {
+    const int k = idx / D, d = idx % D;
+    float s = 0.f;
+    for (int i = 0; i < M; ++i) s += a.e[((int64_t)k * M + i) * D + d];
+    csum[idx] = s;
+    cmean[idx] = s / (float)M;
+  }
+  __threadfence_block();
+  __syncthreads();
+  for (int k = tid; k < N; k += blockDim.x) {
+    float s = 0.f;
+    for (int d = 0; d < D; ++d) s = fmaf(cmean[k * D + d], cmean[k * D + d], s);
+    cnrm[k] = sqrtf(s);
+  }
+  __threadfence_block();
+  __syncthreads();
+
+  float w_loss = 0.f, w_dw = 0.f, w_db = 0.f;  // this wave's partials (same in every lane)
+  for (int row = wave; row < NM; row += GE_WAVES) {
+    const int j = row / M;
+    float ev[GE_DS], cx[GE_DS];
+    float na2 = 0.f, nx2 = 0.f, dot_own = 0.f;
+#pragma unroll
+    for (int s = 0; s < GE_DS; ++s) {
+      const int d = lane + 64 * s;
+      ev[s] = d < D ? a.e[(int64_t)row * D + d] : 0.f;
+      cx[s] = d < D ? (csum[j * D + d] - ev[s]) * inv_m1 : 0.f;
+      na2 = fmaf(ev[s], ev[s], na2);
+      nx2 = fmaf(cx[s], cx[s], nx2);
+      dot_own = fmaf(ev[s], cx[s], dot_own);
+    }
+    const float na_raw = sqrtf(wave_sum(na2)), nx_raw = sqrtf(wave_sum(nx2));
+    const float na = ge_clamp(na_raw), nx = ge_clamp(nx_raw);
+    dot_own = wave_sum(dot_own);
+    const float sim_own = dot_own / (na * nx), s_own = w * sim_own + b;
+    // the hardest negative: first strict maximum of sig~ over k, the own entry standing as 0
+    float best = -1.f, best_dot = 0.f, best_sim = 0.f, best_s = 0.f;
+    int kb = -1;
+    for (int k = 0; k < N; ++k) {
+      float val = 0.f, dot = 0.f, sim = 0.f, S = 0.f;
+      if (k != j) {
+#pragma unroll
+        for (int s = 0; s < GE_DS; ++s) {
+          const int d = lane + 64 * s;
+          dot = fmaf(ev[s], d < D ? cmean[k * D + d] : 0.f, dot);
+        }
+        dot = wave_sum(dot);
+        sim = dot / (na * ge_clamp(cnrm[k]));
+        S = w * sim + b;
+        val = 1.f / (1.f + expf(-S));
+      }
+      // a NaN candidate wins and then stays (the first one), as in torch.max
+      if (val > best || (val != val && best == best))
+        best = val, kb = k, best_dot = dot, best_sim = sim, best_s = S;
+    }
+    const bool neg = kb >= 0 && kb != j;  // a negative won: it carries the second term's gradient
+    const float oms_own = 1.f / (1.f + expf(s_own));
+    const float dS_own = -(1.f - oms_own) * oms_own;
+    const float dS_neg = neg ? best / (1.f + expf(best_s)) : 0.f;
+    w_loss += oms_own + best;
+    w_dw = fmaf(dS_own, sim_own, w_dw);
+    w_dw = fmaf(dS_neg, best_sim, w_dw);
+    w_db += dS_own + dS_neg;
+    if (!grads) continue;
+    // own term: cos(e, x) into e and into the exclude-self centroid x
+    const float ds_o = g * w * dS_own;
+    const float oA = ds_o / (na * nx);
+    const float oBa = na_raw > 1e-8f ? ds_o * dot_own / (na * na * na * nx) : 0.f;
+    const float oBb = nx_raw > 1e-8f ? ds_o * dot_own / (na * nx * nx * nx) : 0.f;
+    // winner's term: cos(e, c_k*) into e; its coefficients into c_k* are left for phase C
+    const int kc = neg ? kb : 0;
+    const float nb_raw = cnrm[kc], nb = ge_clamp(nb_raw);
+    const float ds_n = g * w * dS_neg;
+    const float nA = ds_n / (na * nb);
+    const float nBa = na_raw > 1e-8f ? ds_n * best_dot / (na * na * na * nb) : 0.f;
+    const float nBb = nb_raw > 1e-8f ? ds_n * best_dot / (na * nb * nb * nb) : 0.f;
+#pragma unroll
+    for (int s = 0; s < GE_DS; ++s) {
+      const int d = lane + 64 * s;
+      if (d < D) {
+        float gd = oA * cx[s] - oBa * ev[s];
+        if (neg) gd += nA * cmean[kc * D + d] - nBa * ev[s];
+        a.demb[(int64_t)row * D + d] = gd;
+        dcx[(int64_t)row * D + d] = oA * ev[s] - oBb * cx[s];
+      }
+    }
+    if (lane == 0) {
+      kwin[row] = neg ? kb : -1;
+      coefA[row] = nA;
+      coefB[row] = nBb;
+    }
+  }
+  if (lane == 0) red[wave][0] = w_loss, red[wave][1] = w_dw, red[wave][2] = w_db;
+  __threadfence_block();
+  __syncthreads();
+  if (tid == 0) {
+    float l = 0.f, dw = 0.f, db = 0.f;
+    for (int v = 0; v < GE_WAVES; ++v) l += red[v][0], dw += red[v][1], db += red[v][2];
+    if (a.loss) a.loss[0] = l;
+    if (a.dw) a.dw[0] = g * dw;
+    if (a.db) a.db[0] = g * db;
+  }
+  if (!grads) return;
+  // c_k = csum_k / M: every embedding of speaker k receives dc_k / M
+  for (int idx = tid; idx < N * D; idx += blockDim.x) {
+    const int k = idx / D, d = idx % D;
+    float sa = 0.f, sb = 0.f;
+    for (int row = 0; row < NM; ++row) {
+      if (kwin[row] != k) continue;
+      sa = fmaf(coefA[row], a.e[(int64_t)row * D + d], sa);
+      sb += coefB[row];
+    }
+    dc[idx] = (sa - sb * cmean[idx]) / (float)M;
+  }
+  __threadfence_block();
+  __syncthreads();
+  for (int idx = tid; idx < NM * D; idx += blockDim.x) {
+    const int row = idx / D, d = idx % D, j = row / M, i = row % M;
+    float sx = 0.f;
+    for (int i2 = 0; i2 < M; ++i2)
+      if (i2 != i) sx += dcx[((int64_t)j * M + i2) * D + d];
+    a.demb[idx] += dc[j * D + d] + sx * inv_m1;
+  }
+}
+
 // ---------------------------------------------------------------- Adam, coupled L2 decay
 // torch.optim.Adam(weight_decay = wd): g <- clip_coef g + wd p, then Adam.  The step counter
 // lives on the device; with a gate (device float) of 0 the call is torch's "no parameter has a
@@ -399,6 +553,40 @@ int fs2_ge2e_softmax(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim
   Ge2e a{emb, (int)n_spk, (int)m_utt, (int)dim, w, b, g, loss, demb, dw, db, ws};
   ge2e_softmax_kernel<<<1, 64 * GE_WAVES, 0, st>>>(a);
   return launch_status("fs2_ge2e_softmax");
+}
+
+// fs2_ge2e_softmax's limits, the products taken one at a time (no int64 overflow on any input)
+static bool ge2e_contrast_shape_ok(int64_t n_spk, int64_t m_utt, int64_t dim) {
+  const int64_t lim = 1ll << 28;
+  if (n_spk < 1 || n_spk >= lim || m_utt < 2 || m_utt >= lim || dim < 1 || dim > GE_DMAX)
+    return false;
+  const int64_t nm = n_spk * m_utt;
+  return nm < lim && nm * (n_spk > dim ? n_spk : dim) < lim;
+}
+
+// centroid sums, means and gradients (3 N D), centroid norms (N), per row the winner's index and
+// two coefficients (3 NM) and the gradient into its exclude-self centroid (NM D); 0 for a shape
+// the entry rejects
+int64_t fs2_ge2e_contrast_ws_bytes(int64_t n_spk, int64_t m_utt, int64_t dim) {
+  if (!ge2e_contrast_shape_ok(n_spk, m_utt, dim)) return 0;
+  const int64_t nm = n_spk * m_utt;
+  return (3 * n_spk * dim + n_spk + 3 * nm + nm * dim) * 4;
+}
+
+int fs2_ge2e_contrast(const float* emb, int64_t n_spk, int64_t m_utt, int64_t dim, const float* w,
+                      const float* b, const float* g, float* loss, float* demb, float* dw,
+                      float* db, float* ws, int64_t ws_bytes, void* stream) {
+  FS2_CHECK_ARG(ge2e_contrast_shape_ok(n_spk, m_utt, dim),
+                "fs2_ge2e_contrast: n_spk %lld (>= 1), m_utt %lld (>= 2), dim %lld (1..%d)",
+                (long long)n_spk, (long long)m_utt, (long long)dim, GE_DMAX);
+  FS2_CHECK_ARG(emb && w && b && ws, "fs2_ge2e_contrast: missing operand");
+  FS2_CHECK_ARG(ws_bytes >= fs2_ge2e_contrast_ws_bytes(n_spk, m_utt, dim),
+                "fs2_ge2e_contrast: workspace too small");
+  hipStream_t st = as_stream(stream);
+  poison(ws, ws_bytes, st);
+  Ge2e a{emb, (int)n_spk, (int)m_utt, (int)dim, w, b, g, loss, demb, dw, db, ws};
+  ge2e_contrast_kernel<<<1, 64 * GE_WAVES, 0, st>>>(a);
+  return launch_status("fs2_ge2e_contrast");
 }
 
 int fs2_adam_l2_step(float* p, const float* g, float* m, float* v, int64_t n,

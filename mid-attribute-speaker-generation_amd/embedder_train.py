@@ -31,8 +31,11 @@ waveform through the mel front end (``audio.py``), ``spkr2embedding`` lines 289-
 Not ported: the per-batch random shuffle / unshuffle of lines 160-172 is drawn by the batcher
 (to keep Python's generator in step with the reference) but not applied -- the embedder treats
 the rows independently, so it only changes the order in which the gradient sums run; the
-silence split of ``process_dvector_wav`` (``librosa.effects.split``), the ``contrast`` loss,
-DDP of the embedder, and the joint ``train_ganlike.py`` loop.
+silence split of ``process_dvector_wav`` (``librosa.effects.split``), DDP of the embedder, and
+the joint ``train_ganlike.py`` loop.
+
+``EmbedderTrainer(loss='contrast')`` trains with the reference's other ``hp.model.loss``
+(``utils.get_contrast_loss``, ``fs2_ge2e_contrast``); ``'softmax'`` is the default.
 
 Either architecture of the encoder trains here: pass
 ``SpeechEmbedder(device, True, architecture='rescnn')`` as ``embedder`` for the residual CNN;
@@ -84,13 +87,16 @@ class _Adam:
 
 class EmbedderTrainer:
     def __init__(self, embedder=None, criterion=None, device="cuda", n_utt=10, lr=1e-3,
-                 weight_decay=1e-6, da_startpoint=0.0):
-        """n_utt: utterances per speaker in a batch (hp.train.M)."""
+                 weight_decay=1e-6, da_startpoint=0.0, loss="softmax"):
+        """n_utt: utterances per speaker in a batch (hp.train.M); loss: hp.model.loss,
+        ``'softmax'`` or ``'contrast'``, for the ``GE2ELoss`` made here (a ``criterion`` passed
+        in keeps its own)."""
         self.device = torch.device(device)
         self.n_utt = int(n_utt)
         self.embedder = embedder if embedder is not None else SpeechEmbedder(device, True)
         self.embedder.weight_grads = True
-        self.criterion = criterion if criterion is not None else GE2ELoss(device)
+        self.criterion = criterion if criterion is not None else GE2ELoss(device, loss=loss)
+        self.loss = getattr(self.criterion, "loss", None)  # None: a criterion that names none
         self.da_startpoint = float(da_startpoint)
         e = self.embedder
         self.optimizers = {

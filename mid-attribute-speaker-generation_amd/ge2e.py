@@ -14,8 +14,8 @@ Mirrors ``Multilingual-Speaker-Encoder-with-Domain-Adaptation/speech_embedder_ne
   the GE2E similarity term there has M = 1 utterance per "speaker", for which the
   reference's exclude-self centroid divides by M - 1 = 0 (``utils.py:36``) -- it is NaN and
   returned as NaN here as well.  For M > 1, the speaker-encoder training loss, the softmax
-  GE2E loss is one kernel forward and one backward (``fs2_ge2e_softmax``); the 'contrast'
-  variant is not built and raises.
+  GE2E loss is one kernel forward and one backward (``fs2_ge2e_softmax``), and so is the
+  'contrast' variant (``GE2ELoss(loss='contrast')``, ``hp.model.loss``; ``fs2_ge2e_contrast``).
 * ``SpeechEmbedder(architecture='rescnn')`` -- the reference's other feature extractor
   (``hp.model.architecture``, ``speech_embedder_net.py:19-63,79-81``): a 2-D residual CNN over
   the (mel, time) plane, 640 features, the same head behind a 640-wide projection
@@ -346,22 +346,41 @@ class _GE2ESoftmaxFn(torch.autograd.Function):
         return demb, dw, db
 
 
+class _GE2EContrastFn(torch.autograd.Function):
+    """``get_similarity`` + ``get_contrast_loss`` (utils.py:77-90, 106-124) with ``w sim + b``
+    (speech_embedder_net.py:177), one kernel forward and one backward."""
+
+    @staticmethod
+    def forward(fctx, emb, w, b):
+        fctx.save_for_backward(emb, w, b)
+        return K.ge2e_contrast(emb, w.detach(), b.detach())
+
+    @staticmethod
+    def backward(fctx, g):
+        emb, w, b = fctx.saved_tensors
+        _, demb, dw, db = K.ge2e_contrast(emb, w.detach(), b.detach(), g=g.contiguous(),
+                                          grads=True)
+        return demb, dw, db
+
+
 class GE2ELoss(nn.Module):
-    """``speech_embedder_net.py:165-186`` (softmax GE2E + BCE domain loss)."""
+    """``speech_embedder_net.py:165-186`` (softmax or contrast GE2E + BCE domain loss);
+    ``loss`` is ``hp.model.loss``."""
+
+    _FNS = {"softmax": _GE2ESoftmaxFn, "contrast": _GE2EContrastFn}
 
     def __init__(self, device="cuda", loss="softmax"):
         super().__init__()
+        if loss not in self._FNS:
+            raise ValueError(f"loss {loss!r}: 'softmax' or 'contrast'")
         self.w = nn.Parameter(torch.tensor(10.0, device=device))
         self.b = nn.Parameter(torch.tensor(-5.0, device=device))
         self.loss = loss  # hp.model.loss
 
     def forward(self, embeddings, lang_logits, langs, **kwargs):
         N, M, _ = embeddings.shape
-        if self.loss != "softmax":
-            raise NotImplementedError(f"hp.model.loss == {self.loss!r} is not built (the "
-                                      "reference's config uses 'softmax')")
         if M != 1:
-            loss = _GE2ESoftmaxFn.apply(embeddings.contiguous(), self.w, self.b)
+            loss = self._FNS[self.loss].apply(embeddings.contiguous(), self.w, self.b)
         else:  # utils.py:36, M - 1 = 0
             loss = torch.full((), float("nan"), device=embeddings.device)
         da = _BCESumFn.apply(lang_logits.contiguous(), langs.contiguous().float()) \

@@ -748,6 +748,26 @@ def ge2e_softmax(emb, w, b, g=None, grads=False):
     return (loss, demb, dw, db) if grads else loss
 
 
+def ge2e_contrast(emb, w, b, g=None, grads=False):
+    """GE2E contrast loss of emb (N, M, D); with ``grads`` also (demb, dw, db) scaled by the
+    device scalar ``g`` (fs2_ge2e_contrast).  Off the GPU there is no path: ``NotImplementedError`` (a
+    ``RuntimeError``), as ``GE2ELoss(loss='contrast')`` raised there before the kernel existed."""
+    if not emb.is_cuda:
+        raise NotImplementedError("ge2e_contrast needs tensors on the GPU (no CPU path exists)")
+    _dev(emb, g)
+    N, M, D = emb.shape
+    dev = emb.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    demb = torch.empty_like(emb) if grads else None
+    dw = torch.empty((), dtype=torch.float32, device=dev) if grads else None
+    db = torch.empty((), dtype=torch.float32, device=dev) if grads else None
+    n = lib.fs2_ge2e_contrast_ws_bytes(N, M, D)
+    wk = ws(n, dev)
+    lib.fs2_ge2e_contrast(ptr(emb), N, M, D, ptr(w), ptr(b), ptr(g), ptr(loss), ptr(demb), ptr(dw),
+                          ptr(db), ptr(wk), n, stream())
+    return (loss, demb, dw, db) if grads else loss
+
+
 def mel_crop_gather(store, row_off, row_stride, row_start, n_mels, length, out=None):
     """out[r, t, c] = store[row_off[r] + c * row_stride[r] + row_start[r] + t]: crop, transpose
     and stack utterances of a flat (n_mels, frames)-per-utterance corpus into (rows, length,
