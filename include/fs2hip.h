@@ -1470,6 +1470,57 @@ int fs2_mas(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
             int64_t t_m, int64_t t_s, int64_t* durations, void* ws, int64_t ws_bytes,
             void* stream);
 
+/* ---------------------------------------------------------------- generated-speaker metrics
+ * Not in the reference: set-to-set statistics in speaker-encoder space for speakers that have
+ * no recording to be scored against (csrc/speaker_eval.hip).  No atomics, every
+ * reduction in a fixed order, results independent of the grid; a size of 0 launches nothing.
+ *
+ * fs2_cosine_nn: for every row of a (Na, D) the k nearest rows of b (Nb, D) by cosine distance,
+ * fp32 inputs of any length, 1 <= D <= FS2_NN_MAX_DIM, 1 <= k <= FS2_NN_MAX_K; the Na x Nb
+ * matrix is never stored.  Per pair three fp64 sums dot, |a|^2, |b|^2, each over d = 0 .. D-1 in
+ * that order (a product of two fp32 values is exact in fp64);
+ *   den = sqrt(|a|^2) * sqrt(|b|^2), c = den > 0 ? dot / den : 0, dist = (float)(1.0 - c).
+ * Candidates rank by that fp32 dist, ties to the lower index of b; a NaN distance is never a
+ * candidate.  dist (Na, k) fp32 ascending, index (Na, k) int64; slots without a candidate hold
+ * +inf and -1.  group_a (Na) / group_b (Nb): device int64, both or neither; mode 0 skips
+ * candidate j when group_a[i] == group_b[j], mode 1 keeps only those.  A block owns 16 rows of
+ * a in LDS and sweeps b; past 1024 rows b is cut into ranges of 1024, one block column each,
+ * whose lists are merged in range order (fs2_cosine_nn_ws_bytes holds them) -- the same list,
+ * bit for bit, as one sweep gives.  Nb = 0 writes the empty lists.
+ *
+ * fs2_finite_summary: x (n) fp32, n <= FS2_SUMMARY_MAX_N -> out[5] fp64 = [count of finite
+ * entries, their median as numpy.median has it (the mean of the two middle values for an even
+ * count), their mean summed in fp64 in index order, min, max]; count = 0 gives NaN for the
+ * other four.  The selection is exact: a binary search over the bits of an order-preserving
+ * 32-bit key, one counting pass per bit (ws: fs2_finite_summary_ws_bytes, the keys).
+ *
+ * fs2_gauss_moments: x (n, D) fp32, n >= 2, D <= FS2_FRECHET_MAX_DIM -> mean (D) and the
+ * unbiased covariance cov (D, D), fp64, two passes: the mean (rows in order), then the centred
+ * products (rows in order) / (n - 1).
+ *
+ * fs2_frechet: per pair p of Gaussians, from fp64 moments mean_a / mean_b (P, D) and cov_a /
+ * cov_b (P, D, D), D <= FS2_FRECHET_MAX_DIM, one workgroup with the matrices in LDS:
+ * Sigma_a = V L V^T by cyclic Jacobi (fp64, round-robin pair order, at most 30 sweeps, ended in
+ * the kernel by the first sweep without a rotation), S = V max(L, 0)^(1/2) V^T, mu = the
+ * eigenvalues of sym(S Sigma_b S) by the same solver;
+ *   out[p] = [|dmu|^2 + tr Sigma_a + tr Sigma_b - 2 sum sqrt(max(mu, 0)), |dmu|^2,
+ *             tr Sigma_a + tr Sigma_b, sum sqrt(max(mu, 0))].                                */
+#define FS2_NN_MAX_DIM 256
+#define FS2_NN_MAX_K 16
+#define FS2_SUMMARY_MAX_N 1048576
+#define FS2_FRECHET_MAX_DIM 64
+int64_t fs2_cosine_nn_ws_bytes(int64_t na, int64_t nb, int64_t k);
+int fs2_cosine_nn(const float* a, const float* b, int64_t na, int64_t nb, int64_t dim, int64_t k,
+                  const int64_t* group_a, const int64_t* group_b, int mode, float* dist,
+                  int64_t* index, void* ws, int64_t ws_bytes, void* stream);
+int64_t fs2_finite_summary_ws_bytes(int64_t n);
+int fs2_finite_summary(const float* x, int64_t n, double* out, void* ws, int64_t ws_bytes,
+                       void* stream);
+int fs2_gauss_moments(const float* x, int64_t n, int64_t dim, double* mean, double* cov,
+                      void* stream);
+int fs2_frechet(const double* mean_a, const double* cov_a, const double* mean_b,
+                const double* cov_b, int64_t pairs, int64_t dim, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

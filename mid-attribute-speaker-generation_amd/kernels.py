@@ -1782,3 +1782,77 @@ def mas(logp, src_lens, mel_lens, host_lens=None):
     lib.fs2_mas(ptr(logp), ptr(src_lens), ptr(mel_lens), B, T_m, T_s, ptr(durations), ptr(wk), nb,
                 stream())
     return durations
+
+
+# ------------------------------------------------------------------ generated-speaker metrics
+NN_MAX_DIM = 256           # FS2_NN_MAX_DIM
+NN_MAX_K = 16              # FS2_NN_MAX_K
+SUMMARY_MAX_N = 1 << 20    # FS2_SUMMARY_MAX_N
+FRECHET_MAX_DIM = 64       # FS2_FRECHET_MAX_DIM
+
+
+def cosine_nn(a, b, k=1, group_a=None, group_b=None, same=False):
+    """fs2_cosine_nn: a (Na, D), b (Nb, D) f32 -> ``(dist (Na, k) f32 ascending, index (Na, k)
+    int64)``, the k rows of b nearest to each row of a by cosine distance, ties to the lower
+    index, slots without a candidate +inf / -1.  ``group_a`` (Na) / ``group_b`` (Nb) device
+    int64, both or neither: candidates of the row's own group are skipped, or with ``same`` the
+    only ones kept."""
+    _dev(a, b, group_a, group_b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 2 or b.dim() != 2 or \
+            a.shape[1] != b.shape[1]:
+        raise RuntimeError("cosine_nn: a (Na, D) and b (Nb, D) are f32")
+    (Na, D), Nb, k = a.shape, b.shape[0], int(k)
+    if (group_a is None) != (group_b is None):
+        raise RuntimeError("cosine_nn: the groups come as a pair or not at all")
+    if group_a is not None and (group_a.dtype != torch.int64 or group_b.dtype != torch.int64 or
+                                group_a.numel() != Na or group_b.numel() != Nb):
+        raise RuntimeError(f"cosine_nn: groups are device int64 ({Na}) and ({Nb})")
+    dist = torch.empty((Na, max(k, 0)), dtype=torch.float32, device=a.device)
+    index = torch.empty((Na, max(k, 0)), dtype=torch.int64, device=a.device)
+    nb = lib.fs2_cosine_nn_ws_bytes(Na, Nb, k)
+    wk = torch.empty(max(nb, 1), dtype=torch.uint8, device=a.device)
+    lib.fs2_cosine_nn(ptr(a), ptr(b), Na, Nb, D, k, ptr(group_a), ptr(group_b), int(bool(same)),
+                      ptr(dist), ptr(index), ptr(wk), nb, stream())
+    return dist, index
+
+
+def finite_summary(x):
+    """fs2_finite_summary: x f32 (any shape, at most 2^20 entries) -> f64[5] on the device =
+    [count, median, mean, min, max] of the finite entries (NaN but for the count when none)."""
+    _dev(x)
+    if x.dtype != torch.float32:
+        raise RuntimeError("finite_summary: x is f32")
+    n = x.numel()
+    out = torch.empty(5, dtype=torch.float64, device=x.device)
+    nb = lib.fs2_finite_summary_ws_bytes(n)
+    wk = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+    lib.fs2_finite_summary(ptr(x), n, ptr(out), ptr(wk), nb, stream())
+    return out
+
+
+def gauss_moments(x):
+    """fs2_gauss_moments: x (n, D) f32, n >= 2 -> ``(mean (D), cov (D, D))`` f64, the unbiased
+    covariance, two-pass with the rows in order."""
+    _dev(x)
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise RuntimeError("gauss_moments: x is f32 (n, D)")
+    n, D = x.shape
+    mean = torch.empty(D, dtype=torch.float64, device=x.device)
+    cov = torch.empty((D, D), dtype=torch.float64, device=x.device)
+    lib.fs2_gauss_moments(ptr(x), n, D, ptr(mean), ptr(cov), stream())
+    return mean, cov
+
+
+def frechet(mean_a, cov_a, mean_b, cov_b):
+    """fs2_frechet: f64 moments (D) / (D, D), or batched (P, D) / (P, D, D) -> (P, 4) f64 =
+    [distance, |dmu|^2, tr cov_a + tr cov_b, sum sqrt(eig(S cov_b S))]."""
+    _dev(mean_a, cov_a, mean_b, cov_b)
+    D = mean_a.shape[-1]
+    P = mean_a.numel() // max(D, 1)
+    for m, c in ((mean_a, cov_a), (mean_b, cov_b)):
+        if m.dtype != torch.float64 or c.dtype != torch.float64 or m.numel() != P * D or \
+                c.numel() != P * D * D or c.shape[-2:] != (D, D):
+            raise RuntimeError(f"frechet: moments are f64 ({P}, {D}) and ({P}, {D}, {D})")
+    out = torch.empty((P, 4), dtype=torch.float64, device=mean_a.device)
+    lib.fs2_frechet(ptr(mean_a), ptr(cov_a), ptr(mean_b), ptr(cov_b), P, D, ptr(out), stream())
+    return out

@@ -56,11 +56,18 @@ def synth_dvectors(model, vocoder, trainer, batch, control_values=(1.0, 1.0, 1.0
                     speaker_meta=speaker_meta)
     finally:
         model.train(was)
+    return out, output_dvectors(out, vocoder, trainer, hop_length)
+
+
+@torch.no_grad()
+def output_dvectors(out, vocoder, trainer, hop_length=256):
+    """The vocoder and speaker-encoder leg of ``synth_dvectors`` on a model output tuple (of
+    ``forward`` in eval mode or of ``synthesize_from_speaker_emb``) -> d-vectors (B, 64)."""
     post, mel_len = out[1], out[9]
     B, T, C = post.shape
     wav, _ = vocoder.forward_rows(post.reshape(B * T, C), B, T, pcm=False, lengths=mel_len)
     lens = (mel_len * hop_length).tolist()
-    return out, trainer.dvector_from_wav(wav.view(B, -1), lens=lens)
+    return trainer.dvector_from_wav(wav.view(B, -1), lens=lens)
 
 
 def synthesize(model, configs, vocoder, batchs, control_values):
