@@ -1470,6 +1470,68 @@ int fs2_mas(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
             int64_t t_m, int64_t t_s, int64_t* durations, void* ws, int64_t ws_bytes,
             void* stream);
 
+/* ---------------------------------------------------------------- phoneme error rate
+ * Not in the reference (it judges synthesis by ear): a general CTC loss, the greedy CTC decoder
+ * and a batched edit distance -- csrc/ctc.hip; DESIGN.md §7.  One workgroup per utterance or
+ * pair; lengths are device int64[B], never read back; no atomics, every reduction in a fixed
+ * order: a row's result has the same bits wherever it sits in a batch and from run to run.
+ * batch = 0 launches nothing and returns 0; every argument is checked before any launch.
+ * T <= FS2_CTC_MAX_T, L_max <= FS2_CTC_MAX_TARGET, C <= FS2_CTC_MAX_CLASSES, C <= ld <= 65535,
+ * R_max, H_max <= FS2_EDIT_MAX_LEN, B <= 65535.
+ *
+ * fs2_ctc_loss: logits (B, T, ld) fp32 with C <= ld classes (columns C..ld-1 are never read),
+ * blank in [0, C), targets (B, L_max) int64, M = frame_lens[b] clamped into 1..T, L =
+ * target_lens[b] clamped into 0..L_max (L = 0: the all-blank path), w (B) fp32.  For each frame
+ * t < M the C logits are log-softmaxed (max in fp32, the sum of exp and the log in fp64) and the
+ * CTC recursion runs over the 2L + 1 states z of the blank-interleaved target (z_2k = blank,
+ * z_2k+1 = target[k]), alpha and beta in fp64 in the log domain:
+ *   alpha_0(j) = y_0(z_j) for j < 2, else -inf;
+ *   alpha_t(j) = y_t(z_j) + lse(alpha_t-1(j), alpha_t-1(j-1), [skip] alpha_t-1(j-2)),
+ * the skip open for odd j >= 3 with target[k] != target[k-1] (k = (j-1)/2), beta the mirror
+ * image from beta_M-1(j) = y_M-1(z_j) for j >= 2L - 1; ll = lse(alpha_M-1(2L), alpha_M-1(2L-1)).
+ * nll[b] = -ll (fp32).  grad (B, T, ld) fp32 = d(w[b] nll[b]) / dlogits
+ *   = w[b] (softmax[t, c] - gamma_t(c)),  gamma_t(c) = sum over states j with z_j = c of
+ *     exp(alpha_t(j) + beta_t(j) - y_t(z_j) - ll),
+ * summed in ascending state order in fp64 (the blank column: its L + 1 states in order), a state
+ * whose alpha or beta is -inf at t (a -inf logit masks its class there) counting 0;
+ * exactly 0 for t >= M and in columns C..ld-1.  A row without a valid path -- M < L + the number
+ * of adjacent repeats, a label outside [0, C), a label equal to blank, or scores that give
+ * ll = -inf -- has nll = +inf and grad = 0; nothing out of range is read for it and the other
+ * rows stand.  The workspace (fs2_ctc_loss_ws_bytes = B T (2 L_max + 1) 8) holds every state's
+ * alpha, replaced by its occupancy in the beta sweep.
+ *
+ * fs2_ctc_greedy: the same logits, C, ld, blank and frame_lens.  Per frame t < M the arg-max of
+ * the raw fp32 logits over the C classes: a NaN never wins, ties go to the lowest class, a frame
+ * of nothing but NaN is blank.  Repeats are collapsed, blanks dropped and the labels compacted
+ * in order by a block scan: ids (B, T) int64, 0 at and past lens[b]; lens (B) int64; argmax
+ * (B, T) int32 (nullable), blank at t >= M.
+ *
+ * fs2_edit_distance: ref (B, R_max), hyp (B, H_max) int64, lengths clamped into 0..max (0 is
+ * legal on either side or both).  One Levenshtein table with unit costs, D(i, 0) = i,
+ * D(0, j) = j, D(i, j) = min(D(i-1, j-1) + [ref_i != hyp_j], D(i-1, j) + 1, D(i, j-1) + 1), the
+ * first minimum taken in that order: the diagonal (a match or a substitution), then a deletion
+ * (a reference symbol without a partner), then an insertion.  The path is traced back from
+ * (R, H) in the same launch: out (B, 4) int64 = [distance, substitutions, deletions,
+ * insertions], distance = S + D + I.  Anti-diagonals with the last two in LDS; the workspace
+ * holds one step byte per cell (fs2_edit_distance_ws_bytes = B (R_max + H_max + 1) (R_max + 1)).
+ * All integers: exact.                                                                        */
+#define FS2_CTC_MAX_T 2048
+#define FS2_CTC_MAX_TARGET 1024
+#define FS2_CTC_MAX_CLASSES 1024
+#define FS2_EDIT_MAX_LEN 2048
+int64_t fs2_ctc_loss_ws_bytes(int64_t batch, int64_t t, int64_t l_max);
+int fs2_ctc_loss(const float* logits, const int64_t* targets, const int64_t* frame_lens,
+                 const int64_t* target_lens, const float* w, int64_t batch, int64_t t,
+                 int64_t n_classes, int64_t ld, int64_t blank, int64_t l_max, float* nll,
+                 float* grad, void* ws, int64_t ws_bytes, void* stream);
+int fs2_ctc_greedy(const float* logits, const int64_t* frame_lens, int64_t batch, int64_t t,
+                   int64_t n_classes, int64_t ld, int64_t blank, int64_t* ids, int64_t* lens,
+                   int* argmax, void* stream);
+int64_t fs2_edit_distance_ws_bytes(int64_t batch, int64_t r_max, int64_t h_max);
+int fs2_edit_distance(const int64_t* ref, const int64_t* ref_lens, const int64_t* hyp,
+                      const int64_t* hyp_lens, int64_t batch, int64_t r_max, int64_t h_max,
+                      int64_t* out, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- generated-speaker metrics
  * Not in the reference: set-to-set statistics in speaker-encoder space for speakers that have
  * no recording to be scored against (csrc/speaker_eval.hip).  No atomics, every

@@ -1784,6 +1784,84 @@ def mas(logp, src_lens, mel_lens, host_lens=None):
     return durations
 
 
+# ------------------------------------------------------------------ phoneme error rate
+CTC_MAX_T = 2048         # FS2_CTC_MAX_T
+CTC_MAX_TARGET = 1024    # FS2_CTC_MAX_TARGET
+CTC_MAX_CLASSES = 1024   # FS2_CTC_MAX_CLASSES
+EDIT_MAX_LEN = 2048      # FS2_EDIT_MAX_LEN
+
+
+def _ctc_logits(name, logits, frame_lens, n_classes):
+    _dev(logits)
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise RuntimeError(f"{name}: logits (B, T, ld) are f32")
+    B, T, ld = logits.shape
+    _lens_i64(name, frame_lens, B)
+    return B, T, ld, ld if n_classes is None else int(n_classes)
+
+
+def ctc_loss(logits, targets, frame_lens, target_lens, w, n_classes=None, blank=0, host_lens=None):
+    """fs2_ctc_loss: logits (B, T, ld) f32 whose first ``n_classes`` columns are the classes
+    (default all), targets (B, L_max) int64, device int64 lengths, w (B) f32 -> ``(nll (B) f32,
+    grad (B, T, ld) = d(w[b] nll[b]) / dlogits)``, the gradient 0 past a row's frames and in the
+    columns past the classes.  ``host_lens`` = (target, frame) host lists: a row with fewer frames
+    than labels raises before the launch (on the device a row without a valid path gives nll =
+    +inf and a zero gradient)."""
+    B, T, ld, C = _ctc_logits("ctc_loss", logits, frame_lens, n_classes)
+    _dev(targets, w)
+    if targets.dtype != torch.int64 or targets.dim() != 2 or targets.shape[0] != B:
+        raise RuntimeError(f"ctc_loss: targets are int64 ({B}, L_max)")
+    L_max = targets.shape[1]
+    _lens_i64("ctc_loss", target_lens, B)
+    if w.dtype != torch.float32 or w.numel() != B:
+        raise RuntimeError(f"ctc_loss: w is f32 ({B})")
+    if host_lens is not None:
+        for b, (n, m) in enumerate(zip(*host_lens)):
+            if int(m) < int(n):
+                raise RuntimeError(f"ctc_loss: row {b} has {int(m)} frames for {int(n)} labels "
+                                   "(no valid path)")
+    nll = torch.empty(B, dtype=torch.float32, device=logits.device)
+    grad = torch.empty_like(logits)
+    nb = lib.fs2_ctc_loss_ws_bytes(B, T, L_max)
+    wk = torch.empty(max(nb // 8, 1), dtype=torch.float64, device=logits.device)
+    lib.fs2_ctc_loss(ptr(logits), ptr(targets), ptr(frame_lens), ptr(target_lens), ptr(w), B, T, C,
+                     ld, int(blank), L_max, ptr(nll), ptr(grad), ptr(wk), nb, stream())
+    return nll, grad
+
+
+def ctc_greedy(logits, frame_lens, n_classes=None, blank=0, argmax=False):
+    """fs2_ctc_greedy: per-frame arg-max of the raw logits (ties to the lowest class, a NaN never
+    wins, an all-NaN frame is blank), repeats collapsed, blanks dropped -> ``(ids (B, T) int64, 0
+    past the length, lens (B) int64)``; with ``argmax`` also the per-frame arg-max (B, T)
+    int32."""
+    B, T, ld, C = _ctc_logits("ctc_greedy", logits, frame_lens, n_classes)
+    ids = torch.empty((B, T), dtype=torch.int64, device=logits.device)
+    lens = torch.empty(B, dtype=torch.int64, device=logits.device)
+    am = torch.empty((B, T), dtype=torch.int32, device=logits.device) if argmax else None
+    lib.fs2_ctc_greedy(ptr(logits), ptr(frame_lens), B, T, C, ld, int(blank), ptr(ids), ptr(lens),
+                       ptr(am), stream())
+    return (ids, lens, am) if argmax else (ids, lens)
+
+
+def edit_distance(ref, ref_lens, hyp, hyp_lens):
+    """fs2_edit_distance: ref (B, R_max), hyp (B, H_max) int64 with device int64 lengths ->
+    (B, 4) int64 = [distance, substitutions, deletions, insertions] of the unit-cost Levenshtein
+    alignment, the diagonal preferred to a deletion to an insertion at a tie."""
+    _dev(ref, hyp)
+    if ref.dtype != torch.int64 or hyp.dtype != torch.int64 or ref.dim() != 2 or hyp.dim() != 2 \
+            or ref.shape[0] != hyp.shape[0]:
+        raise RuntimeError("edit_distance: ref (B, R_max) and hyp (B, H_max) are int64")
+    (B, R), H = ref.shape, hyp.shape[1]
+    _lens_i64("edit_distance", ref_lens, B)
+    _lens_i64("edit_distance", hyp_lens, B)
+    out = torch.empty((B, 4), dtype=torch.int64, device=ref.device)
+    nb = lib.fs2_edit_distance_ws_bytes(B, R, H)
+    wk = torch.empty(max(nb, 1), dtype=torch.uint8, device=ref.device)
+    lib.fs2_edit_distance(ptr(ref), ptr(ref_lens), ptr(hyp), ptr(hyp_lens), B, R, H, ptr(out),
+                          ptr(wk), nb, stream())
+    return out
+
+
 # ------------------------------------------------------------------ generated-speaker metrics
 NN_MAX_DIM = 256           # FS2_NN_MAX_DIM
 NN_MAX_K = 16              # FS2_NN_MAX_K

@@ -110,6 +110,40 @@ def compare_wavs(wav_a, lens_a, wav_b, lens_b, front_end, pitch=None, trainer=No
     return rec
 
 
+PER_FIELDS = ("distance", "substitutions", "deletions", "insertions", "phonemes")
+
+
+def phoneme_error_rate(recognizer, mels, mel_lens, texts, src_lens, rows=False):
+    """Intelligibility: the greedy transcription of each mel by ``recognizer`` (a
+    ``recognizer.RecognizerTrainer``) against the phonemes ``texts`` (B, T_s) int64 with lengths
+    ``src_lens``; mels (B, T, n_mels) in the model's row layout, as the PostNet returns them
+    (what they hold past ``mel_lens`` does not matter: the recogniser masks it).
+    Everything stays on the device: the int64 sums ``PER_FIELDS`` = [distance, substitutions,
+    deletions, insertions, reference phonemes] over the batch, to be added up over a pass and
+    given to ``per_from_sums``; with ``rows`` the per-utterance records (B, 4) and the reference
+    lengths (B) instead.
+
+    The PER is that of the project's own small recogniser, trained on the same corpus: it compares
+    runs that share a recogniser checkpoint, and is no word error rate, no substitute for a
+    listening test and nothing across recognisers."""
+    dev = mels.device
+    sl = _lens(src_lens, dev).clamp(0, texts.shape[1])
+    rec = recognizer.errors(mels.contiguous().float(), _lens(mel_lens, dev),
+                            texts.to(device=dev, dtype=torch.int64).contiguous(), sl)
+    if rows:
+        return rec, sl
+    return torch.cat([rec.sum(0), sl.sum().reshape(1)])
+
+
+def per_from_sums(sums):
+    """The figures of a pass from the five sums of ``phoneme_error_rate`` (host ints): ``per`` =
+    sum of distances / sum of reference lengths (insertions count, so it can exceed 1; nan
+    without a reference phoneme) and the parts."""
+    out = {k: int(v) for k, v in zip(PER_FIELDS, sums)}
+    out["per"] = out["distance"] / out["phonemes"] if out["phonemes"] > 0 else float("nan")
+    return out
+
+
 def from_sums(sums, n):
     """The corpus figures from the column sums of ``n`` records (host floats)."""
     sums = [float(s) for s in sums]

@@ -207,10 +207,17 @@ def _text_fields(batch):
 
 @torch.no_grad()
 def synth_speaker_set(model, vocoder, trainer, batches, embs, control_values=(1.0, 1.0, 1.0),
-                      hop_length=256):
+                      hop_length=256, recognizer=None):
     """Every text batch in the voice of every row of ``embs`` (S, d) -> ``SpeakerSet`` of the
-    utterances' d-vectors, speaker-major.  The embedding goes in per batch row, (B, d)."""
+    utterances' d-vectors, speaker-major.  The embedding goes in per batch row, (B, d).  With
+    ``recognizer`` (a ``recognizer.RecognizerTrainer``) the result is ``(SpeakerSet, sums)``:
+    the device int64 sums ``metrics.PER_FIELDS`` of ``metrics.phoneme_error_rate`` of every
+    synthesised mel (``out[1]``, ``out[9]`` frames) against its text."""
     from .synthesize import output_dvectors
+    per_sums = None
+    if recognizer is not None:
+        from . import metrics
+        per_sums = torch.zeros(len(metrics.PER_FIELDS), dtype=torch.int64, device=embs.device)
     p_c, e_c, d_c = control_values
     was = model.training
     model.eval()
@@ -225,11 +232,16 @@ def synth_speaker_set(model, vocoder, trainer, batches, embs, control_values=(1.
                     None, texts, src_lens, max_src_len, p_control=p_c, e_control=e_c,
                     d_control=d_c, accents=accents, speaker_emb=emb)
                 dvecs.append(output_dvectors(out, vocoder, trainer, hop_length))
+                if recognizer is not None:
+                    post = out[1].contiguous()
+                    per_sums += metrics.phoneme_error_rate(
+                        recognizer, post, out[9].clamp(1, post.shape[1]), texts, src_lens)
                 n += texts.shape[0]
             seg.append(seg[-1] + n)
     finally:
         model.train(was)
-    return SpeakerSet(torch.cat(dvecs).contiguous(), seg)
+    out = SpeakerSet(torch.cat(dvecs).contiguous(), seg)
+    return out if recognizer is None else (out, per_sums)
 
 
 def speaker_labels(config_path, metadata, attribute):
@@ -250,7 +262,7 @@ def speaker_labels(config_path, metadata, attribute):
 
 def evaluate_generated(model, vocoder, trainer, batches, priors, n_speakers, train_speakers=None,
                        attribute=None, seed=0, control_values=(1.0, 1.0, 1.0), hop_length=256,
-                       config_path=None):
+                       config_path=None, recognizer=None):
     """The full evaluation: for each named prior (a ``GMMPrior`` from ``speaker_distribution``,
     an ``InterpolateGMM`` at a rate, a ``BarycenterGMM``) draw ``n_speakers`` embeddings
     (``draw``), synthesise every text batch for each of them and for the training speakers
@@ -261,14 +273,30 @@ def evaluate_generated(model, vocoder, trainer, batches, priors, n_speakers, tra
     Returns ``{"tables": {prior: table}, "sets": {"train": SpeakerSet, prior: SpeakerSet}}``; with
     ``attribute`` -- per training speaker of ``train_speakers`` a 0/1 label, or an attribute name
     looked up by ``speaker_labels`` in ``config_path``'s speakers.json -- also ``"vote": {prior: mean
-    attribute_vote of the generated speakers' centroids against the training speakers'}``."""
+    attribute_vote of the generated speakers' centroids against the training speakers'}``.
+
+    With ``recognizer`` (a ``recognizer.RecognizerTrainer``; default None: the keys are those
+    above) also ``"per": {"train": ..., prior: ...}``, per set the phoneme error rate of its
+    synthesised mels against the texts (``metrics.phoneme_error_rate`` on the PostNet mel, no
+    vocoder involved; one host read per set): whether a voice drawn from the prior still speaks
+    the text.  The figures are those of this recogniser checkpoint; see ``metrics``."""
     batches = list(batches)
     table_rows = model.speaker_emb.weight.detach().float()
     ids = list(range(table_rows.shape[0])) if train_speakers is None else \
         [int(s) for s in train_speakers]
     kw = dict(control_values=control_values, hop_length=hop_length)
-    train = synth_speaker_set(model, vocoder, trainer, batches,
-                              table_rows[torch.tensor(ids).to(table_rows.device)].contiguous(), **kw)
+    per = {}
+
+    def synth(name, embs):
+        if recognizer is None:
+            return synth_speaker_set(model, vocoder, trainer, batches, embs, **kw)
+        from . import metrics
+        out, sums = synth_speaker_set(model, vocoder, trainer, batches, embs,
+                                      recognizer=recognizer, **kw)
+        per[name] = metrics.per_from_sums(sums.tolist())["per"]
+        return out
+
+    train = synth("train", table_rows[torch.tensor(ids).to(table_rows.device)].contiguous())
     labels = None
     if isinstance(attribute, str):
         if config_path is None:
@@ -284,13 +312,14 @@ def evaluate_generated(model, vocoder, trainer, batches, priors, n_speakers, tra
         out["vote"] = {}
         ct = centroids(train.dvecs, train.seg_start)
     for name, prior in priors.items():
-        gen = synth_speaker_set(model, vocoder, trainer, batches, draw(prior, n_speakers, seed),
-                                **kw)
+        gen = synth(name, draw(prior, n_speakers, seed))
         out["sets"][name] = gen
         out["tables"][name] = distance_table(train, gen)
         if labels is not None:
             votes = attribute_vote(centroids(gen.dvecs, gen.seg_start), ct, labels)
             out["vote"][name] = summary(votes)["mean"]
+    if recognizer is not None:
+        out["per"] = per
     return out
 
 
@@ -318,14 +347,16 @@ def main(argv=None):
     """``python -m mid-attribute-speaker-generation_amd.speaker_eval -c DIR --restore_step N
     --embedder CKPT [--checkpoint P] [--corpus NAME ...] [--vocoder hifigan|griffinlim]
     [--n_speakers 100] [--n_texts 20] [--attribute gender --rates 0 0.25 0.5 0.75 1] [--seed S]
-    [--out report.json]``
+    [--recognizer CKPT] [--out report.json]``
 
     ``DIR`` is a training config directory (as ``train`` takes).  Texts are the first
     ``n_texts`` utterances of the validation list.  Without ``--rates`` the priors are the
     attribute's two values; with them, ``InterpolateGMM`` between the two at those rates.  The
     report is one JSON object: per prior its table, and with ``--attribute`` the vote (the share
     of a generated speaker's 5 nearest training speakers that carry the attribute's second
-    value) and the ``g2t`` median per rate."""
+    value) and the ``g2t`` median per rate; with ``--recognizer`` (a checkpoint of
+    ``recognize``) ``per``, the phoneme error rate of the training speakers' and of each prior's
+    synthesised mels."""
     import argparse
     import glob
 
@@ -353,7 +384,12 @@ def main(argv=None):
     ap.add_argument("--rates", type=float, nargs="*", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--recognizer", type=str, default=None,
+                    help="a recogniser checkpoint (recognize): add the phoneme error rate of "
+                         "every set's synthesised mels to the report")
     args = ap.parse_args(argv)
+    if args.recognizer is not None and not os.path.isfile(args.recognizer):
+        ap.error(f"--recognizer {args.recognizer}: no such file")
 
     pp, mc, tc, path = cfg.load_configs(args.config)
     model = FastSpeech2(pp, mc, path, device="cuda")
@@ -405,14 +441,21 @@ def main(argv=None):
             priors[f"{attribute}@{t:g}"] = g
     else:
         priors = dict(zip(metadata[attribute], ends))
+    recognizer = None
+    if args.recognizer is not None:
+        from .recognizer import load_recognizer
+        recognizer = load_recognizer(args.recognizer, "cuda")
     res = evaluate_generated(model, vocoder, trainer, batches, priors, args.n_speakers,
                              attribute=args.attribute, seed=args.seed,
-                             hop_length=pp["stft"]["hop_length"], config_path=path)
+                             hop_length=pp["stft"]["hop_length"], config_path=path,
+                             recognizer=recognizer)
     report = {"tables": res["tables"],
               "embedding_space": embedding_space_report(model, priors, args.n_speakers, args.seed),
               "g2t_median": {k: v["g2t"]["median"] for k, v in res["tables"].items()}}
     if "vote" in res:
         report["vote"] = res["vote"]
+    if "per" in res:
+        report["per"] = res["per"]
     text = json.dumps(_jsonable(report), indent=1)
     if args.out:
         with open(args.out, "w") as f:

@@ -544,6 +544,7 @@ def evaluate(model, step, store_or_batcher, Loss, eLoss=None, batch_size=None):
 # ------------------------------------------------------------------ objective synthesis metrics
 SYNTH_MESSAGE = "Synthesis, Step {}, MCD: {:.3f} dB, Length Error: {:+.2%}"
 SYNTH_F0_MESSAGE = ", F0 RMSE: {:.1f} cents, V/UV Error: {:.2%}"
+SYNTH_PER_MESSAGE = ", PER: {:.2%} (recording: {:.2%})"
 
 
 def synthesis_message(step, figures, f0=False):
@@ -551,11 +552,13 @@ def synthesis_message(step, figures, f0=False):
     message = SYNTH_MESSAGE.format(step, figures["mcd_db"], figures["length_error"])
     if f0:
         message += SYNTH_F0_MESSAGE.format(figures["f0_rmse_cents"], figures["vuv_error"])
+    if "per" in figures:
+        message += SYNTH_PER_MESSAGE.format(figures["per"], figures["per_recording"])
     return message
 
 
 def evaluate_synthesis(model, step, store_or_batcher, batch_size=None, vocoder=None, pitch=None,
-                       front_end=None, n_coef=13):
+                       front_end=None, n_coef=13, recognizer=None):
     """What ``evaluate`` cannot say: whether FREE-RUNNING synthesis resembles the recording ->
     ``(dict, message)``.
 
@@ -580,6 +583,15 @@ def evaluate_synthesis(model, step, store_or_batcher, batch_size=None, vocoder=N
     sides pass through the same vocoder, so its own F0 errors largely cancel; the figures say
     nothing about the recording's true F0.
 
+    With ``recognizer`` (a ``recognizer.RecognizerTrainer``; default None: nothing of this
+    happens and the dict and the message are what they are without it) two more fields: ``per``,
+    the phoneme error rate of the free-running PostNet mel against the input phonemes
+    (``metrics.phoneme_error_rate``: greedy CTC transcription, edit distance, sum of distances /
+    sum of phonemes over the pass), and ``per_recording``, the same of the corpus mels of the
+    same utterances -- the recogniser's own floor, without which the first cannot be read.  Both
+    go into the message.  No vocoder is involved: the recogniser reads the mel.  The figures are
+    those of this recogniser checkpoint and compare runs that share it; see ``metrics``.
+
     The model is in train mode afterwards, as after ``evaluate``."""
     from . import metrics
     from .corpus_store import CorpusBatcher, CorpusStore
@@ -597,6 +609,8 @@ def evaluate_synthesis(model, step, store_or_batcher, batch_size=None, vocoder=N
         vocoder = GriffinLim(front_end=front_end)
     n, dev = len(batcher.store), batcher.store.device
     sums = torch.zeros(len(metrics.FIELDS), dtype=torch.float64, device=dev)
+    per_sums = None if recognizer is None else \
+        torch.zeros((2, len(metrics.PER_FIELDS)), dtype=torch.int64, device=dev)
 
     def contour(mel_rows, B, T, lens):
         wav = vocoder.forward_rows(mel_rows.reshape(B * T, -1), B, T, pcm=False, lengths=lens)[0]
@@ -625,9 +639,22 @@ def evaluate_synthesis(model, step, store_or_batcher, batch_size=None, vocoder=N
                 rec = metrics.compare_mels(post, syn_len, ref, ref_len, n_coef=n_coef, f0_a=f0_s,
                                            f0_b=f0_r, rows=True)
                 sums += rec.sum(0)
+                if recognizer is not None:
+                    per_sums[0] += metrics.phoneme_error_rate(recognizer, post, syn_len, batch[3],
+                                                              batch[4])
+                    per_sums[1] += metrics.phoneme_error_rate(recognizer, ref, ref_len, batch[3],
+                                                              batch[4])
     finally:
         model.train()
-    figures = metrics.from_sums(sums.tolist(), n)  # the pass's one host read
+    if recognizer is None:
+        figures = metrics.from_sums(sums.tolist(), n)  # the pass's one host read
+    else:
+        host = torch.cat([sums, per_sums.reshape(-1).double()]).tolist()  # still one read
+        figures = metrics.from_sums(host[:len(metrics.FIELDS)], n)
+        k = len(metrics.PER_FIELDS)
+        for name, row in (("per", 0), ("per_recording", 1)):
+            lo = len(metrics.FIELDS) + row * k
+            figures[name] = metrics.per_from_sums([int(v) for v in host[lo:lo + k]])["per"]
     return figures, synthesis_message(step, figures, f0=pitch is not None)
 
 
@@ -726,8 +753,8 @@ def load_discriminator(train_config, device):
 
 def main(argv=None):
     """``python -m mid-attribute-speaker-generation_amd.train -c DIR [--restore_step N]
-    [--checkpoint P] [--corpus NAME ...] [--use_clf] [--synth_metrics] [--synth_pitch {yin,pyin}]``
-    (``train.py:296-343``).  ``DIR`` holds
+    [--checkpoint P] [--corpus NAME ...] [--use_clf] [--synth_metrics] [--synth_pitch {yin,pyin}]
+    [--synth_recognizer CKPT]`` (``train.py:296-343``).  ``DIR`` holds
     ``preprocess.yaml``, ``model.yaml``, ``train.yaml``, ``stats.json``, ``speakers.json`` and one
     ``preprocess_<corpus>.yaml`` per corpus (all of them in sorted order, or the ``--corpus``
     ones in the order given).  ``--dtype bf16`` runs the bf16 compute path."""
@@ -755,7 +782,15 @@ def main(argv=None):
                          "synthesis against the validation corpus (evaluate_synthesis)")
     ap.add_argument("--synth_pitch", choices=("yin", "pyin"), default="yin",
                     help="the F0 estimator behind --synth_metrics' F0 and V/UV errors")
+    ap.add_argument("--synth_recognizer", type=str, default=None,
+                    help="a recogniser checkpoint (recognize): with --synth_metrics, also log the "
+                         "phoneme error rate of free-running synthesis and of the recordings")
     args = ap.parse_args(argv)
+    if args.synth_recognizer is not None:
+        if not args.synth_metrics:
+            ap.error("--synth_recognizer needs --synth_metrics")
+        if not os.path.isfile(args.synth_recognizer):
+            ap.error(f"--synth_recognizer {args.synth_recognizer}: no such file")
 
     pp, mc, tc, path = cfg.load_configs(args.config)
     if mc.get("jdit", {}).get("use_jdit") or not mc.get("multi_speaker", True):
@@ -811,6 +846,9 @@ def main(argv=None):
             vocoder = GriffinLim(front_end=front_end)
         pitch = PitchExtractor(pp, device="cuda", method=args.synth_pitch)
         synth_eval = dict(vocoder=vocoder, pitch=pitch, front_end=front_end)
+        if args.synth_recognizer is not None:
+            from .recognizer import load_recognizer
+            synth_eval["recognizer"] = load_recognizer(args.synth_recognizer, "cuda")
     print("Number of FastSpeech2 Parameters:", sum(p.numel() for p in model.parameters()))
     last = fit(trainer, CorpusBatcher(train_store, bs), CorpusBatcher(
         val_store, bs, group_size=1, shuffle=False, sort=False, drop_last=False), tc,
