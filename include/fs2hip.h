@@ -1449,7 +1449,32 @@ int fs2_path_metrics(const double* cost, const int* path, const int* path_len, c
  * with the diagonal s - 1 taken on a tie (V[t-1, -1] = -inf); the path ends at (M-1, N-1) and is
  * traced back in the same launch from one step byte per cell in the workspace.  durations
  * (B, T_s) int64 = frames per phoneme, >= 1 for s < N, 0 for s >= N.  A row with M < N has no
- * such path: its durations are all 0 (callers that know the lengths reject it beforehand).   */
+ * such path: its durations are all 0 (callers that know the lengths reject it beforehand).
+ *
+ * Optional positions (fs2_forward_sum_opt, fs2_mas_opt): optional (B, T_s) uint8, read at s < N
+ * only and staged once per row into LDS; a marked position may take no frame (an optional
+ * silence).  A valid labelling keeps every unmarked position, may omit marked ones, never two
+ * neighbours and never all.  Both are defined by the formulas below and memory-safe for any mask
+ * content; callers reject rows with two adjacent marks or no unmarked position.  Workspaces,
+ * limits and argument checks are those of fs2_forward_sum / fs2_mas, plus optional != NULL; with
+ * an all-zero mask the results are theirs bit for bit (the extra terms are summed last, and an
+ * exp of -inf adds an exact 0).
+ *
+ * fs2_forward_sum_opt: the states are the pairs bl[s] (the blank before label s, s = 0..N) and
+ * la[s]; omitting a marked label u omits the pair (la[u], bl[u+1]), so a labelling keeps exactly
+ * one state path.  Beside the edges of fs2_forward_sum: into la[s] when optional[s-1] from
+ * bl[s-1] and, for s >= 2, from la[s-2]; when optional[0] and N >= 2, la[1] is an initial state
+ * too; when optional[N-1] and N >= 2, la[N-2] and bl[N-1] are final states too; beta the mirror
+ * image.  grad[t, s] = w[b] (softmax_t(s) - occupancy_t(la[s])).  Whether a path exists is found
+ * after the alpha pass: ll = -inf gives nll[b] = +inf and a gradient that is exactly 0.
+ *
+ * fs2_mas_opt: V[0, 0] = logp[0, 0]; V[0, 1] = logp[0, 1] when optional[0] and N >= 2; the rest
+ * of row 0 is -inf.  Among V[t-1, s-1] and V[t-1, s] the diagonal wins a tie; V[t-1, s-2] is a
+ * candidate only when optional[s-1] and s >= 2, and is taken only when strictly greater than
+ * that winner.  The path ends at (M-1, N-1), or at (M-1, N-2) when optional[N-1], N >= 2 and
+ * V[M-1, N-2] is strictly greater.  Step byte per cell: 0 stay, 1 diagonal, 2 skip; the
+ * trace-back does s -= step.  durations >= 1 for kept positions, 0 for omitted ones, their sum M;
+ * a row without a path (its end cell is -inf) gets all zeros.   */
 #define FS2_ALIGN_MAX_SRC 1024
 #define FS2_ALIGN_MAX_MEL 2048
 #define FS2_ALIGN_MAX_WIDTH 128
@@ -1469,6 +1494,13 @@ int64_t fs2_mas_ws_bytes(int64_t batch, int64_t t_m, int64_t t_s);
 int fs2_mas(const float* logp, const int64_t* src_lens, const int64_t* mel_lens, int64_t batch,
             int64_t t_m, int64_t t_s, int64_t* durations, void* ws, int64_t ws_bytes,
             void* stream);
+int fs2_forward_sum_opt(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
+                        const unsigned char* optional, const float* w, int64_t batch, int64_t t_m,
+                        int64_t t_s, float* nll, float* grad, void* ws, int64_t ws_bytes,
+                        void* stream);
+int fs2_mas_opt(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
+                const unsigned char* optional, int64_t batch, int64_t t_m, int64_t t_s,
+                int64_t* durations, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- phoneme error rate
  * Not in the reference (it judges synthesis by ear): a general CTC loss, the greedy CTC decoder

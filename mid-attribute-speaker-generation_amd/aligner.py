@@ -145,34 +145,38 @@ class AlignerTrainer:
         q, k = self.model(texts, mels)
         return _LogProbFn.apply(q, k, src_lens, mel_lens, self.temperature, self.omega)
 
-    def backward(self, texts, src_lens, mels, mel_lens, host_lens=None):
+    def backward(self, texts, src_lens, mels, mel_lens, host_lens=None, optional=None):
         """The device loss, its parameter gradients left in ``arena.grad`` (``train_step`` without
         the update).  The forward-sum kernel returns the loss's gradient with the loss, so the
-        graph is entered at ``logp`` with it."""
+        graph is entered at ``logp`` with it.  ``optional`` (B, T_s) uint8 on the device marks
+        positions that may take no frame (``K.forward_sum``); ``host_lens`` then carries the
+        mask's host copy as its third member."""
         self.arena.zero_grad()
         w = (1.0 / texts.shape[0]) / mel_lens.clamp(1, mels.shape[1]).to(torch.float32)
         logp = self.logprob(texts, src_lens, mels, mel_lens)
-        nll, grad = K.forward_sum(logp.detach(), src_lens, mel_lens, w, host_lens)
+        nll, grad = K.forward_sum(logp.detach(), src_lens, mel_lens, w, host_lens, optional)
         logp.backward(grad)
         return torch.dot(nll, w)
 
-    def train_step(self, texts, src_lens, mels, mel_lens, host_lens=None):
-        loss = self.backward(texts, src_lens, mels, mel_lens, host_lens)
+    def train_step(self, texts, src_lens, mels, mel_lens, host_lens=None, optional=None):
+        loss = self.backward(texts, src_lens, mels, mel_lens, host_lens, optional)
         self.step += 1
         bc1, bc2 = 1.0 - BETAS[0] ** self.step, 1.0 - BETAS[1] ** self.step
         K.adam_step(self.arena.flat, self.arena.grad, self.m, self.v, None, self.lr, BETAS[0],
                     BETAS[1], EPS, bc1, bc2 ** 0.5)
         return loss
 
-    def align(self, texts, src_lens, mels, mel_lens, host_lens=None):
-        """durations (B, T_s) int64 on the device: frames per phoneme, 0 past a row's phonemes."""
+    def align(self, texts, src_lens, mels, mel_lens, host_lens=None, optional=None):
+        """durations (B, T_s) int64 on the device: frames per phoneme, 0 past a row's phonemes
+        and at an ``optional`` position that the path omits."""
         with torch.no_grad():
             return K.mas(self.logprob(texts, src_lens, mels, mel_lens), src_lens, mel_lens,
-                         host_lens)
+                         host_lens, optional)
 
     def fit(self, batches, steps):
         """``steps`` updates over ``batches``, an iterable of ``(texts, src_lens, mels, mel_lens)``
-        (cycled when it is a list); returns the device losses."""
+        or, with optional positions, ``(texts, src_lens, mels, mel_lens, optional)`` (cycled when
+        it is a list); returns the device losses."""
         losses, it = [], None
         while len(losses) < steps:
             if it is None:
@@ -184,7 +188,7 @@ class AlignerTrainer:
                     raise ValueError("no batches") from None
                 it = None
                 continue
-            losses.append(self.train_step(*batch))
+            losses.append(self.train_step(*batch[:4], optional=batch[4] if len(batch) > 4 else None))
         return losses
 
     def save(self, path):

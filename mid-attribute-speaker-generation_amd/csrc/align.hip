@@ -6,6 +6,8 @@
 //   align_logprob_bwd   dq, dk from dL/dlogp, the softmax recomputed
 //   forward_sum         the CTC forward-sum loss over the target 1..N and its gradient
 //   mas                 monotonic alignment search: the best monotonic path as durations
+// and forward_sum_opt / mas_opt, the last two over a source sequence whose marked positions (the
+// optional silences) may take no frame.
 //
 // The distance-softmax kernels own a tile of AL_TT frames with the tile's whole score rows in LDS
 // (AL_TT x T_s floats), so a row is written once, normalised.  The two dynamic programmes run one
@@ -427,6 +429,277 @@ __global__ __launch_bounds__(AL_T) void mas_kernel(
   for (int s = tid; s < T_s; s += AL_T) out[s] = s < N ? (int64_t)dur[s] : 0;
 }
 
+// ---------------------------------------------------------------- optional positions
+// A position s < N with optional[s] != 0 may take no frame (an optional silence).  The row's mask
+// is staged once into LDS as bytes, 0 at s >= N, so that the sweeps read it beside the state rows.
+FS2_DEV void al_stage_mask(const unsigned char* __restrict__ optional, int N, int T_s,
+                           unsigned char* op) {
+  for (int s = threadIdx.x; s < T_s; s += AL_T) op[s] = s < N && optional[s] ? 1 : 0;
+  __syncthreads();
+}
+
+// the extra terms come last: an exp of -inf adds an exact 0, so with none of them open these are
+// the bits of lse2 / lse3
+FS2_DEV double lse4(double a, double b, double c, double d) {
+  const double m = fmax(fmax(a, fmax(b, c)), d);
+  if (m == -INFINITY) return -INFINITY;
+  return m + log(exp(a - m) + exp(b - m) + exp(c - m) + exp(d - m));
+}
+FS2_DEV double lse5(double a, double b, double c, double d, double e) {
+  const double m = fmax(fmax(fmax(a, fmax(b, c)), d), e);
+  if (m == -INFINITY) return -INFINITY;
+  return m + log(exp(a - m) + exp(b - m) + exp(c - m) + exp(d - m) + exp(e - m));
+}
+FS2_DEV double lse2x(double a, double b, double c) {  // lse2 and one extra term
+  const double m = fmax(fmax(a, b), c);
+  if (m == -INFINITY) return -INFINITY;
+  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
+}
+
+// forward_sum_kernel with skippable labels.  Omitting a marked label u omits the pair (la[u],
+// bl[u+1]), so a labelling keeps exactly one state path.  Beside the edges of forward_sum_kernel:
+//   into la[s], optional[s-1]:  from bl[s-1] and, s >= 2, from la[s-2]
+//   optional[0], N >= 2:        la[1] is an initial state too
+//   optional[N-1], N >= 2:      la[N-2] and bl[N-1] are final states too
+// beta the mirror image: bl[s] -> la[s+1] when optional[s], la[s] -> la[s+2] when optional[s+1].
+// Whether a path exists is known after the alpha pass (ll = -inf: nll = +inf, gradient 0).
+__global__ __launch_bounds__(AL_T) void forward_sum_opt_kernel(
+    const float* __restrict__ logp, const int64_t* __restrict__ src_lens,
+    const int64_t* __restrict__ mel_lens, const unsigned char* __restrict__ optional,
+    const float* __restrict__ w, int T_m, int T_s, float* __restrict__ nll,
+    float* __restrict__ grad, double* __restrict__ alpha_ws) {
+  extern __shared__ double fs_lds[];
+  __shared__ double ll_s;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int N = al_len(src_lens[b], T_s), M = al_len(mel_lens[b], T_m);
+  const float* lp = logp + (int64_t)b * T_m * T_s;
+  float* gr = grad + (int64_t)b * T_m * T_s;
+  double* aw = alpha_ws + (int64_t)b * T_m * T_s;
+  const int P = T_s + 1;                  // pitch of a state row
+  double* norm = fs_lds;                  // T_m: the log-sum-exp of frame t's N + 1 scores
+  double* rows = fs_lds + T_m;            // 2 buffers x {la, bl} x P
+  unsigned char* op = (unsigned char*)(rows + 4 * P);  // T_s: the row's mask
+  al_stage_mask(optional + (int64_t)b * T_s, N, T_s, op);
+  // the frames' normalisers, a wave per frame
+  for (int t = wave; t < M; t += AL_W) {
+    const float* row = lp + (int64_t)t * T_s;
+    float m = -1.f;  // the blank's score
+    for (int s = lane; s < N; s += 64) m = fmaxf(m, row[s]);
+    m = wave_max(m);
+    double sum = 0.0;
+    for (int s = lane; s < N; s += 64) sum += exp((double)row[s] - (double)m);
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum += exp(-1.0 - (double)m);
+    if (lane == 0) norm[t] = (double)m + log(sum);
+  }
+  __syncthreads();
+  const double ninf = -INFINITY;
+  const bool head = N >= 2 && op[0], tail = N >= 2 && op[N - 1];
+  float el[AL_SI], el_next[AL_SI];
+  bool o_prev[AL_SI], o_self[AL_SI], o_next[AL_SI];  // optional[s-1], [s], [s+1]
+#pragma unroll
+  for (int i = 0; i < AL_SI; ++i) {
+    const int s = tid + i * AL_T;
+    o_prev[i] = s >= 1 && s <= N && op[s - 1];
+    o_self[i] = s < N && op[s];
+    o_next[i] = s + 1 < N && op[s + 1];
+  }
+  // ---- alpha, forward
+#pragma unroll
+  for (int i = 0; i < AL_SI; ++i) {
+    const int s = tid + i * AL_T;
+    el_next[i] = s < N ? lp[s] : 0.f;
+  }
+  for (int t = 0; t < M; ++t) {
+    double* cur = rows + (t & 1) * 2 * P;
+    const double* prv = rows + ((t + 1) & 1) * 2 * P;
+    const double nt = norm[t], eb = -1.0 - nt;
+#pragma unroll
+    for (int i = 0; i < AL_SI; ++i) {
+      el[i] = el_next[i];
+      const int s = tid + i * AL_T;
+      if (t + 1 < M && s < N) el_next[i] = lp[(int64_t)(t + 1) * T_s + s];
+    }
+#pragma unroll
+    for (int i = 0; i < AL_SI; ++i) {
+      const int s = tid + i * AL_T;
+      if (s > N) continue;
+      double ab, al = ninf;
+      if (t == 0) {
+        ab = s == 0 ? eb : ninf;
+        if (s == 0 || (s == 1 && head)) al = (double)el[i] - nt;
+      } else {
+        const double pl1 = s > 0 ? prv[s - 1] : ninf;  // la s-1
+        const double pb = prv[P + s];
+        ab = eb + lse2(pb, pl1);
+        if (s < N) {
+          if (o_prev[i]) {
+            const double pb1 = prv[P + s - 1];               // bl s-1
+            const double pl2 = s >= 2 ? prv[s - 2] : ninf;   // la s-2
+            al = (double)el[i] - nt + lse5(prv[s], pb, pl1, pb1, pl2);
+          } else {
+            al = (double)el[i] - nt + lse3(prv[s], pb, pl1);
+          }
+        }
+      }
+      cur[P + s] = ab;
+      if (s < N) {
+        cur[s] = al;
+        aw[(int64_t)t * T_s + s] = al;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const double* last = rows + ((M - 1) & 1) * 2 * P;
+    ll_s = tail ? lse4(last[P + N], last[N - 1], last[N - 2], last[P + N - 1])
+                : lse2(last[P + N], last[N - 1]);
+    nll[b] = (float)-ll_s;
+  }
+  __syncthreads();
+  const double ll = ll_s;
+  if (ll == ninf) {  // no valid path
+    for (int64_t e = tid; e < (int64_t)T_m * T_s; e += AL_T) gr[e] = 0.f;
+    return;
+  }
+  const double wb = (double)w[b];
+  // ---- beta, backward, combined with alpha on the fly
+  double a_next[AL_SI], a_cur[AL_SI];
+#pragma unroll
+  for (int i = 0; i < AL_SI; ++i) {
+    const int s = tid + i * AL_T;
+    el_next[i] = s < N ? lp[(int64_t)(M - 1) * T_s + s] : 0.f;
+    a_next[i] = s < N ? aw[(int64_t)(M - 1) * T_s + s] : 0.0;
+  }
+  for (int t = M - 1; t >= 0; --t) {
+    double* cur = rows + (t & 1) * 2 * P;
+    const double* nxt = rows + ((t + 1) & 1) * 2 * P;
+    const double nt = norm[t], eb = -1.0 - nt;
+#pragma unroll
+    for (int i = 0; i < AL_SI; ++i) {
+      el[i] = el_next[i];
+      a_cur[i] = a_next[i];
+      const int s = tid + i * AL_T;
+      if (t > 0 && s < N) {
+        el_next[i] = lp[(int64_t)(t - 1) * T_s + s];
+        a_next[i] = aw[(int64_t)(t - 1) * T_s + s];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < AL_SI; ++i) {
+      const int s = tid + i * AL_T;
+      if (s > N) continue;
+      const double e = (double)el[i] - nt;
+      double bb, bl = ninf;
+      if (t == M - 1) {
+        bb = s == N || (s == N - 1 && tail) ? eb : ninf;
+        if (s == N - 1 || (s == N - 2 && tail)) bl = e;
+      } else {
+        const double nb = nxt[P + s];
+        if (s < N) {
+          // bl s -> la s+1 over an omitted label s
+          bb = eb + (o_self[i] && s + 1 < N ? lse2x(nb, nxt[s], nxt[s + 1]) : lse2(nb, nxt[s]));
+          const double nl1 = s + 1 < N ? nxt[s + 1] : ninf;
+          // la s -> la s+2 over an omitted label s+1
+          bl = e + (o_next[i] && s + 2 < N ? lse4(nxt[s], nxt[P + s + 1], nl1, nxt[s + 2])
+                                            : lse3(nxt[s], nxt[P + s + 1], nl1));
+        } else {
+          bb = eb + nb;
+        }
+      }
+      cur[P + s] = bb;
+      if (s < N) {
+        cur[s] = bl;
+        // d nll / d logp[t, s] = softmax_t(s) - occupancy_t(label s)
+        const double occ = exp(a_cur[i] + bl - e - ll);
+        gr[(int64_t)t * T_s + s] = (float)(wb * (exp(e) - occ));
+      }
+    }
+    __syncthreads();
+  }
+  // dead cells
+  for (int64_t e = tid; e < (int64_t)T_m * T_s; e += AL_T) {
+    const int t = (int)(e / T_s), s = (int)(e % T_s);
+    if (t >= M || s >= N) gr[e] = 0.f;
+  }
+}
+
+// mas_kernel with skippable positions: V[t-1, s-2] is a third candidate where optional[s-1], taken
+// only when strictly greater than the winner of the other two; V[0, 1] is a start where
+// optional[0], and (M-1, N-2) the end where optional[N-1] and it is strictly greater.  The step
+// byte is what the trace-back subtracts from s: 0 stay, 1 diagonal, 2 skip.  A row whose end cell
+// is -inf has no path: all zeros.
+__global__ __launch_bounds__(AL_T) void mas_opt_kernel(
+    const float* __restrict__ logp, const int64_t* __restrict__ src_lens,
+    const int64_t* __restrict__ mel_lens, const unsigned char* __restrict__ optional, int T_m,
+    int T_s, int64_t* __restrict__ durations, unsigned char* __restrict__ steps_ws) {
+  __shared__ float V[2][FS2_ALIGN_MAX_SRC];
+  __shared__ int dur[FS2_ALIGN_MAX_SRC];
+  __shared__ unsigned char op[FS2_ALIGN_MAX_SRC];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int N = al_len(src_lens[b], T_s), M = al_len(mel_lens[b], T_m);
+  int64_t* out = durations + (int64_t)b * T_s;
+  const float* lp = logp + (int64_t)b * T_m * T_s;
+  unsigned char* st = steps_ws + (int64_t)b * T_m * T_s;
+  al_stage_mask(optional + (int64_t)b * T_s, N, T_s, op);
+  const bool head = N >= 2 && op[0], tail = N >= 2 && op[N - 1];
+  float x[AL_MI], x_next[AL_MI];
+  bool o_prev[AL_MI];  // optional[s-1], s >= 2
+#pragma unroll
+  for (int i = 0; i < AL_MI; ++i) {
+    const int s = tid + i * AL_T;
+    x_next[i] = s < N ? lp[s] : 0.f;
+    o_prev[i] = s >= 2 && s < N && op[s - 1];
+    if (s < T_s) dur[s] = 0;
+  }
+  for (int t = 0; t < M; ++t) {
+    float* cur = V[t & 1];
+    const float* prv = V[(t + 1) & 1];
+#pragma unroll
+    for (int i = 0; i < AL_MI; ++i) {
+      x[i] = x_next[i];
+      const int s = tid + i * AL_T;
+      if (t + 1 < M && s < N) x_next[i] = lp[(int64_t)(t + 1) * T_s + s];
+    }
+#pragma unroll
+    for (int i = 0; i < AL_MI; ++i) {
+      const int s = tid + i * AL_T;
+      if (s >= N) continue;
+      if (t == 0) {
+        cur[s] = s == 0 || (s == 1 && head) ? x[i] : -INFINITY;
+      } else {
+        const float dg = s > 0 ? prv[s - 1] : -INFINITY, up = prv[s];
+        const bool diag = dg >= up;
+        float best = diag ? dg : up;
+        int step = diag ? 1 : 0;
+        if (o_prev[i]) {
+          const float sk = prv[s - 2];
+          if (sk > best) {
+            best = sk;
+            step = 2;
+          }
+        }
+        cur[s] = __fadd_rn(x[i], best);
+        st[(int64_t)t * T_s + s] = (unsigned char)step;
+      }
+    }
+    __syncthreads();  // row t complete (and, in global memory, its step bytes for this block)
+  }
+  if (tid == 0) {
+    const float* last = V[(M - 1) & 1];
+    int s = N - 1;
+    if (tail && last[N - 2] > last[N - 1]) s = N - 2;
+    if (last[s] != -INFINITY) {
+      for (int t = M - 1; t >= 0; --t) {
+        ++dur[s];
+        if (t > 0) s = max(0, s - (int)st[(int64_t)t * T_s + s]);
+      }
+    }
+  }
+  __syncthreads();
+  for (int s = tid; s < T_s; s += AL_T) out[s] = s < N ? (int64_t)dur[s] : 0;
+}
+
 static bool al_dims_ok(int64_t t_m, int64_t t_s) {
   return t_m >= 1 && t_m <= FS2_ALIGN_MAX_MEL && t_s >= 1 && t_s <= FS2_ALIGN_MAX_SRC;
 }
@@ -549,6 +822,47 @@ int fs2_mas(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
   mas_kernel<<<(unsigned)batch, AL_T, 0, st>>>(logp, src_lens, mel_lens, (int)t_m, (int)t_s,
                                                durations, (unsigned char*)ws);
   return launch_status("fs2_mas");
+}
+
+int fs2_forward_sum_opt(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
+                        const unsigned char* optional, const float* w, int64_t batch, int64_t t_m,
+                        int64_t t_s, float* nll, float* grad, void* ws, int64_t ws_bytes,
+                        void* stream) {
+  FS2_CHECK_ARG(al_dims_ok(t_m, t_s), "fs2_forward_sum_opt: T_m %lld (1..%d), T_s %lld (1..%d)",
+                (long long)t_m, FS2_ALIGN_MAX_MEL, (long long)t_s, FS2_ALIGN_MAX_SRC);
+  FS2_CHECK_ARG(al_batch_ok(batch), "fs2_forward_sum_opt: batch %lld (0..65535)",
+                (long long)batch);
+  if (batch == 0) return FS2_OK;
+  FS2_CHECK_ARG(logp && src_lens && mel_lens && optional && w && nll && grad && ws,
+                "fs2_forward_sum_opt: missing operand");
+  FS2_CHECK_ARG(ws_bytes >= fs2_forward_sum_ws_bytes(batch, t_m, t_s),
+                "fs2_forward_sum_opt: workspace %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)fs2_forward_sum_ws_bytes(batch, t_m, t_s));
+  hipStream_t st = as_stream(stream);
+  poison(ws, ws_bytes, st);
+  const size_t lds = (size_t)(t_m + 4 * (t_s + 1)) * sizeof(double) + (size_t)t_s;
+  forward_sum_opt_kernel<<<(unsigned)batch, AL_T, lds, st>>>(
+      logp, src_lens, mel_lens, optional, w, (int)t_m, (int)t_s, nll, grad, (double*)ws);
+  return launch_status("fs2_forward_sum_opt");
+}
+
+int fs2_mas_opt(const float* logp, const int64_t* src_lens, const int64_t* mel_lens,
+                const unsigned char* optional, int64_t batch, int64_t t_m, int64_t t_s,
+                int64_t* durations, void* ws, int64_t ws_bytes, void* stream) {
+  FS2_CHECK_ARG(al_dims_ok(t_m, t_s), "fs2_mas_opt: T_m %lld (1..%d), T_s %lld (1..%d)",
+                (long long)t_m, FS2_ALIGN_MAX_MEL, (long long)t_s, FS2_ALIGN_MAX_SRC);
+  FS2_CHECK_ARG(al_batch_ok(batch), "fs2_mas_opt: batch %lld (0..65535)", (long long)batch);
+  if (batch == 0) return FS2_OK;
+  FS2_CHECK_ARG(logp && src_lens && mel_lens && optional && durations && ws,
+                "fs2_mas_opt: missing operand");
+  FS2_CHECK_ARG(ws_bytes >= fs2_mas_ws_bytes(batch, t_m, t_s),
+                "fs2_mas_opt: workspace %lld bytes, %lld needed", (long long)ws_bytes,
+                (long long)fs2_mas_ws_bytes(batch, t_m, t_s));
+  hipStream_t st = as_stream(stream);
+  poison(ws, ws_bytes, st);
+  mas_opt_kernel<<<(unsigned)batch, AL_T, 0, st>>>(logp, src_lens, mel_lens, optional, (int)t_m,
+                                                   (int)t_s, durations, (unsigned char*)ws);
+  return launch_status("fs2_mas_opt");
 }
 
 }  // extern "C"

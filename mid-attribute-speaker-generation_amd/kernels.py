@@ -1752,33 +1752,77 @@ def align_logprob_bwd(q, k, g, src_lens, mel_lens, temperature):
     return dq, dk
 
 
-def forward_sum(logp, src_lens, mel_lens, w, host_lens=None):
+def _align_optional(name, optional, B, T_s, host_lens):
+    """The device mask of ``forward_sum`` / ``mas``; with ``host_lens`` = (src, mel, mask), the
+    mask's host copy (B, >= N), the rows are checked before any launch: two adjacent marks or no
+    unmarked position is a ``ValueError``, fewer frames than unmarked positions has no path."""
+    _dev(optional)
+    if optional.dtype != torch.uint8 or tuple(optional.shape) != (B, T_s) or \
+            not optional.is_contiguous():
+        raise RuntimeError(f"{name}: optional is uint8 ({B}, {T_s}), contiguous")
+    if host_lens is None:
+        return
+    if len(host_lens) < 3:
+        raise RuntimeError(f"{name}: with a mask host_lens is (src, mel, the mask's host copy)")
+    for b, (n, m, row) in enumerate(zip(*host_lens)):
+        n = int(n)
+        marks = [bool(v) for v in list(row)[:n]]
+        if len(marks) < n:
+            raise RuntimeError(f"{name}: row {b}: a host mask of {len(marks)} for {n} positions")
+        if any(x and y for x, y in zip(marks, marks[1:])):
+            raise ValueError(f"{name}: row {b} has two adjacent optional positions")
+        need = n - sum(marks)
+        if n >= 1 and need == 0:
+            raise ValueError(f"{name}: row {b} has no position that is not optional")
+        if int(m) < need:
+            raise RuntimeError(f"{name}: row {b} has {int(m)} frames for {need} phonemes "
+                               "(no monotonic path)")
+
+
+def forward_sum(logp, src_lens, mel_lens, w, host_lens=None, optional=None):
     """fs2_forward_sum: the CTC forward-sum loss of the target 1..N under logp (blank score -1)
     -> ``(nll (B) f32, grad (B, T_m, T_s) = d(nll[b] w[b]) / dlogp)``.  ``host_lens`` = (src, mel)
     host lists: a row with fewer frames than phonemes raises before the launch (on the device
-    such a row gives nll = +inf and a zero gradient)."""
+    such a row gives nll = +inf and a zero gradient).  ``optional`` (B, T_s) uint8 on the device:
+    fs2_forward_sum_opt, marked positions may take no frame; ``host_lens`` is then (src, mel,
+    the mask's host copy), see ``_align_optional``."""
     B, T_m, T_s = _align_logp("forward_sum", logp, src_lens, mel_lens)
     _dev(w)
     if w.dtype != torch.float32 or w.numel() != B:
         raise RuntimeError(f"forward_sum: w is f32 ({B})")
-    _align_path_exists("forward_sum", host_lens)
+    if optional is not None:
+        _align_optional("forward_sum", optional, B, T_s, host_lens)
+    else:
+        _align_path_exists("forward_sum", host_lens)
     nll = torch.empty(B, dtype=torch.float32, device=logp.device)
     grad = torch.empty_like(logp)
     nb = lib.fs2_forward_sum_ws_bytes(B, T_m, T_s)
     wk = torch.empty(max(nb // 8, 1), dtype=torch.float64, device=logp.device)
+    if optional is not None:
+        lib.fs2_forward_sum_opt(ptr(logp), ptr(src_lens), ptr(mel_lens), ptr(optional), ptr(w), B,
+                                T_m, T_s, ptr(nll), ptr(grad), ptr(wk), nb, stream())
+        return nll, grad
     lib.fs2_forward_sum(ptr(logp), ptr(src_lens), ptr(mel_lens), ptr(w), B, T_m, T_s, ptr(nll),
                         ptr(grad), ptr(wk), nb, stream())
     return nll, grad
 
 
-def mas(logp, src_lens, mel_lens, host_lens=None):
+def mas(logp, src_lens, mel_lens, host_lens=None, optional=None):
     """fs2_mas: monotonic alignment search -> durations (B, T_s) int64, frames per phoneme (>= 1
-    below a row's phoneme count, 0 past it).  ``host_lens`` as in ``forward_sum``."""
+    below a row's phoneme count, 0 past it).  ``host_lens`` as in ``forward_sum``.  ``optional``
+    (B, T_s) uint8 on the device: fs2_mas_opt, a marked position the path omits has 0 frames."""
     B, T_m, T_s = _align_logp("mas", logp, src_lens, mel_lens)
-    _align_path_exists("mas", host_lens)
+    if optional is not None:
+        _align_optional("mas", optional, B, T_s, host_lens)
+    else:
+        _align_path_exists("mas", host_lens)
     durations = torch.empty((B, T_s), dtype=torch.int64, device=logp.device)
     nb = lib.fs2_mas_ws_bytes(B, T_m, T_s)
     wk = torch.empty(max(nb, 1), dtype=torch.uint8, device=logp.device)
+    if optional is not None:
+        lib.fs2_mas_opt(ptr(logp), ptr(src_lens), ptr(mel_lens), ptr(optional), B, T_m, T_s,
+                        ptr(durations), ptr(wk), nb, stream())
+        return durations
     lib.fs2_mas(ptr(logp), ptr(src_lens), ptr(mel_lens), B, T_m, T_s, ptr(durations), ptr(wk), nb,
                 stream())
     return durations

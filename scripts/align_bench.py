@@ -2,6 +2,8 @@
 
 * ``align_logprob`` forward, ``align_logprob_bwd``, ``forward_sum``, ``mas``: device events around
   one call, the median of ``--reps`` repeats after a warm-up, with (min, max);
+* ``forward_sum_opt`` / ``mas_opt``: the same two on the same ``logp`` with a mask -- all zero
+  (the bits of the plain entries), and every fourth position optional;
 * ``train_step``: one ``AlignerTrainer.train_step`` (channels 64) on the same batch, likewise;
 * ``oracle_cpu``: the numpy / torch oracle (tests/align_oracle.py) on the same batch, wall clock
   per part, and whether the device's results agree with it.
@@ -77,6 +79,19 @@ def main():
     logp = K.align_logprob(dq_, dk_, src, mel, temperature, omega)
     out["forward_sum"] = spread(timed(lambda: K.forward_sum(logp, src, mel, w), args.reps))
     out["mas"] = spread(timed(lambda: K.mas(logp, src, mel), args.reps))
+    for name, step in (("zero_mask", 0), ("every_4th", 4)):
+        mask = torch.zeros((B, N), dtype=torch.uint8, device="cuda")
+        if step:
+            mask[:, ::step] = 1
+        out[f"forward_sum_opt_{name}"] = spread(timed(
+            lambda: K.forward_sum(logp, src, mel, w, optional=mask), args.reps))
+        out[f"mas_opt_{name}"] = spread(timed(
+            lambda: K.mas(logp, src, mel, optional=mask), args.reps))
+    zero = torch.zeros((B, N), dtype=torch.uint8, device="cuda")
+    out["zero_mask_bits_equal"] = bool(
+        torch.equal(K.forward_sum(logp, src, mel, w, optional=zero)[1],
+                    K.forward_sum(logp, src, mel, w)[1]) and
+        torch.equal(K.mas(logp, src, mel, optional=zero), K.mas(logp, src, mel)))
 
     model = AL.Aligner(100, 80, 64, A, "cuda")
     trainer = AL.AlignerTrainer(model, temperature=temperature, omega=omega)
