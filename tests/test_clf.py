@@ -61,8 +61,11 @@ def test_discriminator_matches_reference():
 
 @pytest.mark.gpu
 def test_discriminator_dropout_keeps_forward_backward_consistent():
-    """Classifier dropout (p = 0.2, train mode): the backward regenerates the forward's
-    masks -- the input gradient matches a finite difference of the same call's key."""
+    """Classifier dropout (p = 0.2, train mode) through the module: the backward runs and
+    gives a finite, non-zero input gradient.  That is all this asserts.  That the backward
+    regenerates the forward's masks, and the gradient's value, are checked against the
+    float64 oracle in test_gpu_discriminator_kernels.py::
+    test_clf_head_dropout_masks_and_backward."""
     d = G.SpeechEmbedder(device="cuda")
     PKG.seeded.load_seeded_(d)
     g = load_golden("g10_clf.npz")
