@@ -179,6 +179,60 @@ int fs2_vocoder_post(int dtype, const void* x, int64_t rows, int64_t seq_len, in
                      const int64_t* lens, const float* w, const float* bias, float max_wav_value,
                      float* wav, int16_t* pcm, void* stream);
 
+/* ---------------------------------------------------------------- vocoder training
+ * The generator's backward (hifigan/models.py:155-171 under autograd).  The data gradient of
+ * every convolution is fs2_conv_gemm_ex on dy with fs2_conv_weight_prep's w_bwd; the entry
+ * points below are the rest.
+ *
+ * Weight (and optionally bias) gradient of a dilated Conv1d, accumulated into the fp32
+ * master layout (c_out, c_in, taps):
+ *   dw[o, c, j] += sum_r dy[r, o] * x[r + j*dilation - pad, c]   (x zero outside the utterance
+ *                                                                 of seq_len rows)
+ *   db[o]       += sum_r dy[r, o]                                (db may be NULL)
+ * Any c_in, c_out >= 1, 1 <= taps <= 11, dilation >= 1, 0 <= pad <= (taps-1)*dilation;
+ * rows = batch x seq_len (anything else is an argument error).  dy
+ * (rows, ldy) and x (rows, ldx) are both FS2_F32 (exact f32 MFMA) or both FS2_BF16 (bf16 MFMA,
+ * fp32 accumulate).  64 (o) x 64 (j*c_in + c) output tiles; the rows are cut into `splits`
+ * equal ranges (a multiple of 32 rows each), one fp32 slab per range in ws, and a second
+ * launch adds the slabs to dw / db in a fixed order (eight partial sums, sum g over the
+ * ranges g, g + 8, ... ascending, then added for g = 0..7): no atomics, bitwise reproducible
+ * for the same inputs.  splits = 1 once the tiles alone fill the device (the wide stages), else up to
+ * rows / 128 (the narrow stages' long reductions); fs2_conv_wgrad_dil_ws_bytes holds the rule.
+ * The phase form of a transposed conv is taps = 3, pad = 1 over s*c_out columns; fold its
+ * result with fs2_convT_wgrad_fold.  Replaces the weight half of ConvolutionBackward for
+ * models.py:30-46,113-137.                                                                */
+int64_t fs2_conv_wgrad_dil_ws_bytes(int64_t rows, int64_t c_in, int64_t c_out, int taps);
+int fs2_conv_wgrad_dil(int dtype, const void* dy, int64_t ldy, const void* x, int64_t ldx,
+                       float* dw, float* db, int64_t rows, int64_t seq_len, int64_t c_in,
+                       int64_t c_out, int taps, int pad, int dilation, float* ws,
+                       int64_t ws_bytes, void* stream);
+
+/* Leaky-ReLU backward: dx[i] (+)= dy[i] * (v[i] > 0 ? 1 : alpha)   (torch's convention at 0).
+ * v (dtype FS2_F32 or FS2_BF16) is the saved pre-activation or its leaky-ReLU'd copy -- the
+ * same sign for alpha > 0, and the forward already stores the copies as the next conv's input.
+ * dy, dx fp32; accumulate != 0 adds to dx.  dx may alias dy.                               */
+int fs2_lrelu_bwd(int dtype, const void* v, const float* dy, float* dx, int64_t n, float alpha,
+                  int accumulate, void* stream);
+
+/* Backward of fs2_vocoder_post (conv_post + tanh, no lens): g[r] = d_wav[r] (1 - wav[r]^2),
+ *   dx[r, c]   = sum_j g[r - j + 3] w[c*7 + j]      (rows of the same utterance only)
+ *   dw[c*7+j] += sum_r g[r] x[r + j - 3, c],   db[0] += sum_r g[r]
+ * x (rows, c_in) in `dtype`, 1 <= c_in <= 64; wav the saved output; dx fp32 (rows, c_in),
+ * nullable.  Blocks of 128 rows put their partial dw / db into ws, a second launch adds them
+ * in block order (fixed summation order).                                                 */
+int64_t fs2_vocoder_post_bwd_ws_bytes(int64_t rows, int64_t c_in);
+int fs2_vocoder_post_bwd(int dtype, const void* x, const float* wav, const float* d_wav,
+                         int64_t rows, int64_t seq_len, int64_t c_in, const float* w, float* dx,
+                         float* dw, float* db, float* ws, int64_t ws_bytes, void* stream);
+
+/* The inverse index map of fs2_convT_weight_prep: the gradient dwc (stride*c_out, c_in, 3) of
+ * the 3-tap phase form goes back to the ConvTranspose1d layout,
+ *   dw[c, o, k] += dwc[ph*c_out + o, c, d + 1],  k = ph + stride/2 - stride*d
+ * (every k in [0, 2 stride) has exactly one (ph, d)), and
+ *   db[o] += sum_ph dbc[ph*c_out + o]   in phase order (dbc, db nullable together).       */
+int fs2_convT_wgrad_fold(const float* dwc, const float* dbc, int64_t c_in, int64_t c_out,
+                         int stride, float* dw, float* db, void* stream);
+
 /* ---------------------------------------------------------------- language discriminator
  * The --use_clf branch (train.py:168-197): GE2E SpeechEmbedder (speech_embedder_net.py:65-162)
  * and GE2ELoss's BCE term (165-186), fp32.
@@ -447,6 +501,34 @@ int fs2_melspec(const float* wav, const int64_t* lens, int64_t batch, int64_t sa
                 const int32_t* fb_first, const int32_t* fb_count, const int32_t* fb_off,
                 const float* fb_w, int64_t n_weights, int64_t n_mels, int clip, int log_mag,
                 float* mel, float* energy, float* mag, int64_t* n_frames, void* stream);
+/* The exact adjoint of fs2_melspec's mel output (clip = 0, log_mag = 0) for the vocoder's mel
+ * loss: wav, lens and the tables as fs2_melspec takes them, d_mel (batch, n_mels, F_max) the
+ * cotangent of mel (entries at f >= n_frames are not read), d_wav (batch, samples) its pull-back
+ * (zeros at t >= len).  Each live frame's spectrum is recomputed as fs2_melspec computes it;
+ * then the log clamp (zero where filterbank . mag <= 1e-5, else 1 / it), the filterbank (bin
+ * k sums its filters in ascending order), the modulus (dX = dmag X / |X|, 0 where |X| = 0),
+ * the adjoint of the one-sided transform (d frame[n] = Re sum_{k=0}^{512} dX[k] e^{+2 pi i k n
+ * / 1024}: bins 0 and 512 are real and count once, which is not irfft's weighting) and the
+ * window.  The windowed frames go to ws (batch, F_max, 1024); a second launch sums, per
+ * sample t, every (frame, offset) that fs2_melspec's index rule maps to t -- the position
+ * itself, its reflections about 0 and len - 1 and, at t = 0, everything the final clamp sends
+ * there -- frames ascending.  No atomics: a row's result is bitwise batch invariant.
+ * 128 <= hop <= 512 (the LDS plan of the Griffin-Lim step), n_mels <= 128.                 */
+int64_t fs2_melspec_bwd_ws_bytes(int64_t batch, int64_t samples, int64_t hop);
+int fs2_melspec_bwd(const float* wav, const int64_t* lens, int64_t batch, int64_t samples,
+                    int64_t n_fft, int64_t hop, const float* window, const float* twiddle,
+                    const int32_t* fb_first, const int32_t* fb_count, const int32_t* fb_off,
+                    const float* fb_w, int64_t n_weights, int64_t n_mels, const float* d_mel,
+                    float* d_wav, float* ws, int64_t ws_bytes, void* stream);
+/* loss[0] = mean_i |a[i] - b[i]| as a device scalar and, when d_a is given,
+ * d_a[i] = sign(a[i] - b[i]) / n (0 at equality).  Fixed order: with P = min(1024, ceil(n /
+ * 256)) blocks, thread t of block p sums elements i = 256 p + t + 256 P m (m ascending), the
+ * block reduces them as a binary tree into its partial in ws; a second launch adds the P
+ * partials in order and divides.  All sums in fp64: the loss is the correctly rounded mean.
+ * ws: fs2_mel_l1_ws_bytes() bytes.                                                        */
+int64_t fs2_mel_l1_ws_bytes(void);
+int fs2_mel_l1(const float* a, const float* b, int64_t n, float* loss, float* d_a, float* ws,
+               int64_t ws_bytes, void* stream);
 /* Griffin-Lim (common/audio_processing.py:86-102 over STFT.inverse, common/stft.py:107-137, and
  * TacotronSTFT._mel_to_linear, common/layers.py:125-131): the inverse half of fs2_melspec's
  * transform pair.  Built for n_fft = win_length = 1024 (513 bins) and 128 <= hop <= 512; anything

@@ -71,7 +71,8 @@ def _fold_weight_norm(sd):
 
 
 class Generator(nn.Module):
-    """``hifigan/models.py:104-178`` (inference; weights are fp32 masters, never trained)."""
+    """``hifigan/models.py:104-178``: inference (``forward`` / ``forward_rows``) and, through
+    ``forward_train``, training of the folded fp32 masters (``vocoder_train``)."""
 
     def __init__(self, h, device="cuda", compute_dtype=torch.bfloat16):
         super().__init__()
@@ -282,6 +283,222 @@ class Generator(nn.Module):
         c_last = ch // 2 ** self.num_upsamples
         return K.vocoder_post(h_c, rows, seq, c_last, prep["post_w"], self.conv_post.bias,
                               max_wav_value, pcm=pcm, lens=L(self.num_upsamples + 1))
+
+
+    # ---------------------------------------------------------------- training
+    def weights_changed(self):
+        """Call after the parameters were written behind torch's back (the trainer's flat Adam
+        step): the compute-layout weights are rebuilt at the next forward."""
+        self._prepared = None
+
+    def _prep_train(self):
+        """Compute-layout weights of one training step: every conv's ``w_fwd`` and ``w_bwd``
+        (the data gradient's flipped / transposed form), rebuilt from the masters on each
+        call -- the masters move every step."""
+        cdt = self.compute_dtype
+
+        def conv(w):
+            c_out, c_in, k = w.shape
+            wf = torch.empty(c_out * c_in * k, dtype=cdt, device=w.device)
+            wb = torch.empty(c_out * c_in * k, dtype=cdt, device=w.device)
+            K.weight_prep(w.detach().contiguous(), c_out, c_in, k, w_fwd=wf, w_bwd=wb)
+            return wf, wb
+
+        prep = {"pre": conv(self.conv_pre.weight), "ups": [], "rb": []}
+        for i, m in enumerate(self.ups):
+            wc, bc = K.convT_weight_prep(m.weight.detach().contiguous(), m.bias.detach(),
+                                         self.h.upsample_rates[i])
+            prep["ups"].append((conv(wc), bc))
+        for rb in self.resblocks:
+            prep["rb"].append(([conv(c.weight) for c in rb.convs1],
+                               [conv(c.weight) for c in rb.convs2]))
+        prep["post_w"] = self.conv_post.weight.detach().reshape(-1).contiguous()
+        return prep
+
+    def forward_train(self, mel_rows, B, T):
+        """mel_rows (B*T, 80) -> waveform (B*T*up,) fp32 with a backward: the differentiable
+        ``forward_rows`` (same launches conv by conv, never the fused resblock; in fp32 mode,
+        where ``forward_rows`` takes the per-conv path too, the two waveforms are bitwise
+        equal, which the tests assert).  The backward accumulates ``.grad`` of the plain (folded) fp32 masters -- weight
+        norm is not re-parametrised -- and returns the gradient of ``mel_rows`` when that
+        requires one.  Every conv's input copy and the waveform are saved; nothing is
+        recomputed.  Parameters are switched to ``requires_grad`` on the first call."""
+        params = list(self.parameters())
+        for p in params:
+            if not p.requires_grad:
+                p.requires_grad_(True)
+        self._prepared = None  # training moves the masters: inference re-prepares
+        return _GeneratorTrainFn.apply(self, B, T, mel_rows, *params)
+
+    def _train_fwd(self, mel_rows, B, T):
+        """The per-conv forward of ``forward_rows`` keeping what the backward reads."""
+        prep = self._prep_train()
+        cdt, dev = self.compute_dtype, mel_rows.device
+        x_c = mel_rows.detach().contiguous()
+        if x_c.dtype != cdt:
+            x_c = K.cast_bf16(x_c.float()) if cdt == torch.bfloat16 else x_c.float()
+        rows, seq = B * T, T
+        ch = self.h.upsample_initial_channel
+        h_c = torch.empty(rows, ch, dtype=cdt, device=dev)
+        K.conv_gemm_ex(x_c, prep["pre"][0], rows, seq, x_c.shape[1], ch, 7, 3,
+                       bias=self.conv_pre.bias, y2=h_c, alpha2=LRELU_SLOPE)
+        saved = {"prep": prep, "x_c": x_c, "h": [h_c], "xl": [], "rb": [], "B": B, "T": T}
+        nk = self.num_kernels
+        for i in range(self.num_upsamples):
+            s = self.h.upsample_rates[i]
+            c_in, c_out = ch // 2 ** i, ch // 2 ** (i + 1)
+            (wk, _), bc = prep["ups"][i]
+            x = torch.empty(rows * s, c_out, dtype=torch.float32, device=dev)
+            xl = torch.empty(rows * s, c_out, dtype=cdt, device=dev)
+            K.conv_gemm_ex(h_c, wk, rows, seq, c_in, s * c_out, 3, 1, bias=bc,
+                           out=x.view(rows, s * c_out), y2=xl.view(rows, s * c_out),
+                           alpha2=LRELU_SLOPE)
+            rows, seq = rows * s, seq * s
+            xs = torch.empty(rows, c_out, dtype=torch.float32, device=dev)
+            last_stage = i == self.num_upsamples - 1
+            h_c = torch.empty(rows, c_out, dtype=cdt, device=dev)
+            saved["xl"].append(xl)
+            for j in range(nk):
+                rb = self.resblocks[i * nk + j]
+                w1, w2 = prep["rb"][i * nk + j]
+                k = rb.kernel_size
+                cur, cur_l = x, xl
+                keep = []  # per pair: (c1's input copy, c2's input copy)
+                for m, d in enumerate(rb.dilation):
+                    t_c = torch.empty(rows, c_out, dtype=cdt, device=dev)
+                    K.conv_gemm_ex(cur_l, w1[m][0], rows, seq, c_out, c_out, k, get_padding(k, d),
+                                   dilation=d, bias=rb.convs1[m].bias, flags=K.EPI_LRELU,
+                                   alpha=LRELU_SLOPE, out=t_c)
+                    keep.append((cur_l, t_c))
+                    if m < 2:
+                        nxt = torch.empty(rows, c_out, dtype=torch.float32, device=dev)
+                        nxt_l = torch.empty(rows, c_out, dtype=cdt, device=dev)
+                        K.conv_gemm_ex(t_c, w2[m][0], rows, seq, c_out, c_out, k, get_padding(k, 1),
+                                       bias=rb.convs2[m].bias, flags=K.EPI_ADD_AUX, aux=cur,
+                                       out=nxt, y2=nxt_l, alpha2=LRELU_SLOPE)
+                        cur, cur_l = nxt, nxt_l
+                    else:
+                        fin = j == nk - 1
+                        K.conv_gemm_ex(t_c, w2[m][0], rows, seq, c_out, c_out, k, get_padding(k, 1),
+                                       bias=rb.convs2[m].bias,
+                                       flags=K.EPI_ADD_AUX | (K.EPI_ACC_Y if j > 0 else 0),
+                                       aux=cur, out=xs, y2=h_c if fin else None,
+                                       scale=1.0 / nk if fin else 1.0,
+                                       alpha2=0.01 if last_stage else LRELU_SLOPE)
+                saved["rb"].append(keep)
+            saved["h"].append(h_c)
+        c_last = ch // 2 ** self.num_upsamples
+        wav, _ = K.vocoder_post(h_c, rows, seq, c_last, prep["post_w"], self.conv_post.bias,
+                                pcm=False)
+        saved["wav"] = wav
+        return wav, saved
+
+    def _train_bwd(self, saved, d_wav, want_mel):
+        """Gradients of every parameter and of the mel input, from the waveform's cotangent.
+        Every kernel here accumulates, so where each parameter already holds a contiguous fp32
+        ``.grad`` (the trainer's flat gradient buffer) the sums go straight into it and the
+        returned list holds None; else they go to one flat zeroed buffer whose views (in
+        ``parameters()`` order) are returned for autograd to accumulate."""
+        prep, B, T = saved["prep"], saved["B"], saved["T"]
+        cdt = self.compute_dtype
+        dev = d_wav.device
+        params = list(self.parameters())
+        direct = all(p.grad is not None and p.grad.dtype == torch.float32 and
+                     p.grad.is_contiguous() and p.grad.shape == p.shape for p in params)
+        grads = {}
+        if direct:
+            grads = {id(p): p.grad for p in params}
+        else:
+            flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+            off = 0
+            for p in params:
+                grads[id(p)] = flat[off:off + p.numel()].view(p.shape)
+                off += p.numel()
+        G = lambda p: grads[id(p)]  # noqa: E731
+        C = (lambda t: K.cast_bf16(t)) if cdt == torch.bfloat16 else (lambda t: t)
+        nk, ch = self.num_kernels, self.h.upsample_initial_channel
+        ups = list(self.h.upsample_rates)
+        rows, seq = B * T * math.prod(ups), T * math.prod(ups)
+        c_last = ch // 2 ** self.num_upsamples
+        # the head: d h_c (the leaky-ReLU'd average of the last stage)
+        d_h = K.vocoder_post_bwd(saved["h"][-1], saved["wav"], d_wav.contiguous().float(), rows,
+                                 seq, c_last, prep["post_w"], G(self.conv_post.weight).view(-1),
+                                 G(self.conv_post.bias))
+        for i in reversed(range(self.num_upsamples)):
+            s = ups[i]
+            c_in, c_out = ch // 2 ** i, ch // 2 ** (i + 1)
+            last_stage = i == self.num_upsamples - 1
+            # h_c = leaky_relu(mean of the resblocks): each resblock's output receives g
+            g = K.lrelu_bwd(saved["h"][i + 1], d_h, 0.01 if last_stage else LRELU_SLOPE)
+            K.scale_(g, 1.0 / nk)
+            d_x = None
+            for j in range(nk):
+                rb = self.resblocks[i * nk + j]
+                w1, w2 = prep["rb"][i * nk + j]
+                k = rb.kernel_size
+                keep = saved["rb"][i * nk + j]
+                d_out, owned = g, False
+                for m in (2, 1, 0):
+                    d = rb.dilation[m]
+                    cur_l, t_c = keep[m]
+                    dy = C(d_out)
+                    K.conv_wgrad_dil(dy, t_c, G(rb.convs2[m].weight), rows, seq, c_out, c_out, k,
+                                     get_padding(k, 1), 1, db=G(rb.convs2[m].bias))
+                    d_t = torch.empty(rows, c_out, dtype=torch.float32, device=dev)
+                    K.conv_gemm_ex(dy, w2[m][1], rows, seq, c_out, c_out, k,
+                                   (k - 1) - get_padding(k, 1), out=d_t)
+                    K.lrelu_bwd(t_c, d_t, LRELU_SLOPE, out=d_t)
+                    dy = C(d_t)
+                    K.conv_wgrad_dil(dy, cur_l, G(rb.convs1[m].weight), rows, seq, c_out, c_out, k,
+                                     get_padding(k, d), d, db=G(rb.convs1[m].bias))
+                    # a conv never writes the buffer it reads (in fp32 mode dy IS d_t): other
+                    # blocks of the launch still read those rows as their taps' halo
+                    d_c = torch.empty(rows, c_out, dtype=torch.float32, device=dev)
+                    K.conv_gemm_ex(dy, w1[m][1], rows, seq, c_out, c_out, k,
+                                   (k - 1) * d - get_padding(k, d), dilation=d, out=d_c)
+                    if not owned:  # g is shared by the stage's resblocks
+                        d_out, owned = g.clone(), True
+                    K.lrelu_bwd(cur_l, d_c, LRELU_SLOPE, out=d_out, accumulate=True)
+                d_x = d_out if d_x is None else K.add(d_x, d_out, out=d_x)
+            # the transposed conv in its phase form: (rows, c_out) == (rows / s, s * c_out)
+            rows, seq = rows // s, seq // s
+            (_, wkb), _ = prep["ups"][i]
+            dy = C(d_x).view(rows, s * c_out)
+            dwc = torch.zeros(s * c_out, c_in, 3, dtype=torch.float32, device=dev)
+            dbc = torch.zeros(s * c_out, dtype=torch.float32, device=dev)
+            K.conv_wgrad_dil(dy, saved["h"][i], dwc, rows, seq, c_in, s * c_out, 3, 1, 1, db=dbc)
+            K.convT_wgrad_fold(dwc, dbc, G(self.ups[i].weight), G(self.ups[i].bias), s)
+            d_h = torch.empty(rows, c_in, dtype=torch.float32, device=dev)
+            K.conv_gemm_ex(dy, wkb, rows, seq, s * c_out, c_in, 3, 1, out=d_h)
+        K.lrelu_bwd(saved["h"][0], d_h, LRELU_SLOPE, out=d_h)
+        dy = C(d_h)
+        x_c = saved["x_c"]
+        K.conv_wgrad_dil(dy, x_c, G(self.conv_pre.weight), rows, seq, x_c.shape[1], ch, 7, 3, 1,
+                         db=G(self.conv_pre.bias))
+        d_mel = None
+        if want_mel:
+            d_mel = torch.empty(rows, x_c.shape[1], dtype=torch.float32, device=dev)
+            K.conv_gemm_ex(dy, prep["pre"][1], rows, seq, ch, x_c.shape[1], 7, 3, out=d_mel)
+        return [None if direct else G(p) for p in params], d_mel
+
+
+class _GeneratorTrainFn(torch.autograd.Function):
+    """``Generator.forward_train``: inputs (generator, B, T, mel_rows, *parameters)."""
+
+    @staticmethod
+    def forward(ctx, gen, B, T, mel_rows, *params):
+        wav, saved = gen._train_fwd(mel_rows, B, T)
+        ctx.gen, ctx.saved = gen, saved
+        ctx.mel_dtype = mel_rows.dtype
+        return wav
+
+    @staticmethod
+    def backward(ctx, d_wav):
+        grads, d_mel = ctx.gen._train_bwd(ctx.saved, d_wav, ctx.needs_input_grad[3])
+        ctx.saved = None
+        if d_mel is not None and d_mel.dtype != ctx.mel_dtype:
+            d_mel = d_mel.to(ctx.mel_dtype)
+        return (None, None, None, d_mel) + tuple(grads)
 
 
 def get_vocoder(config=None, device="cuda", ckpt=None, compute_dtype=torch.bfloat16):

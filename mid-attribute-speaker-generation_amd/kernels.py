@@ -147,6 +147,9 @@ def conv_gemm_ex(x, wk, rows, seq_len, c_in, c_out, taps, pad, dilation=1, bias=
         raise RuntimeError(f"conv_gemm_ex operand dtypes differ: {x.dtype} vs {wk.dtype}")
     if out is None and y2 is None:
         raise RuntimeError("conv_gemm_ex: give out and/or y2")
+    if any(t is not None and t.data_ptr() == x.data_ptr() for t in (out, y2)):
+        raise RuntimeError("conv_gemm_ex: an output must not be the input buffer (other blocks "
+                           "of the launch read its rows as their taps' halo)")
     if y2 is not None:
         if y2.dtype != x.dtype or y2.shape != (rows, c_out):
             raise RuntimeError("conv_gemm_ex: y2 must be (rows, c_out) in the compute dtype")
@@ -280,6 +283,126 @@ def cast_bf16(x):
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     lib.fs2_cast_bf16(ptr(x), ptr(y), x.numel(), stream())
     return y
+
+
+# ------------------------------------------------------------------ vocoder training
+def _f32(name, *ts):
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: fp32 tensors expected, got {t.dtype}")
+
+
+def conv_wgrad_dil(dy, x, dw, rows, seq_len, c_in, c_out, taps, pad, dilation=1, db=None,
+                   ws_buf=None):
+    """dw (c_out, c_in, taps) += the weight gradient of a dilated conv; db += column sums of dy
+    when given (fs2_conv_wgrad_dil).  dy (rows, c_out) and x (rows, c_in) fp32 or bf16 (same)."""
+    _dev(dy, x, dw, db, ws_buf)
+    if dy.dtype != x.dtype:
+        raise RuntimeError(f"conv_wgrad_dil operand dtypes differ: {dy.dtype} vs {x.dtype}")
+    _f32("conv_wgrad_dil", dw, db)
+    if dy.numel() != rows * c_out or x.numel() != rows * c_in or \
+            dw.numel() != c_out * c_in * taps or (db is not None and db.numel() != c_out):
+        raise RuntimeError("conv_wgrad_dil: dy (rows, c_out), x (rows, c_in), dw (c_out, c_in, taps), "
+                           "db (c_out)")
+    n = lib.fs2_conv_wgrad_dil_ws_bytes(rows, c_in, c_out, taps)
+    if ws_buf is not None:
+        if ws_buf.numel() * 4 < n:
+            raise RuntimeError("conv_wgrad_dil: workspace too small")
+        w, n = ws_buf, ws_buf.numel() * 4
+    else:
+        w = ws(n, dy.device)
+    lib.fs2_conv_wgrad_dil(code(dy.dtype), ptr(dy), c_out, ptr(x), c_in, ptr(dw), ptr(db), rows,
+                           seq_len, c_in, c_out, taps, pad, dilation, ptr(w), n, stream())
+
+
+def lrelu_bwd(v, dy, alpha, out=None, accumulate=False):
+    """dx (+)= dy * (v > 0 ? 1 : alpha) (fs2_lrelu_bwd): v fp32 or bf16, dy / dx fp32."""
+    _dev(v, dy, out)
+    _f32("lrelu_bwd", dy, out)
+    if v.numel() != dy.numel():
+        raise RuntimeError("lrelu_bwd: v and dy differ in size")
+    if out is None:
+        if accumulate:
+            raise RuntimeError("lrelu_bwd: accumulate needs out")
+        out = torch.empty(dy.shape, dtype=torch.float32, device=dy.device)
+    elif out.numel() != dy.numel():
+        raise RuntimeError("lrelu_bwd: out and dy differ in size")
+    lib.fs2_lrelu_bwd(code(v.dtype), ptr(v), ptr(dy), ptr(out), dy.numel(), float(alpha),
+                      int(bool(accumulate)), stream())
+    return out
+
+
+def vocoder_post_bwd(x, wav, d_wav, rows, seq_len, c_in, w, dw, db, want_dx=True):
+    """Backward of ``vocoder_post`` (fs2_vocoder_post_bwd): returns dx (rows, c_in) fp32 (or
+    None); dw (c_in * 7) and db (1) accumulate."""
+    _dev(x, wav, d_wav, w, dw, db)
+    _f32("vocoder_post_bwd", wav, d_wav, w, dw, db)
+    if x.numel() != rows * c_in or wav.numel() != rows or d_wav.numel() != rows or \
+            w.numel() != 7 * c_in or dw.numel() != 7 * c_in or db.numel() != 1:
+        raise RuntimeError("vocoder_post_bwd: x (rows, c_in), wav / d_wav (rows), w / dw (c_in * 7), db (1)")
+    dx = torch.empty(rows, c_in, dtype=torch.float32, device=x.device) if want_dx else None
+    n = lib.fs2_vocoder_post_bwd_ws_bytes(rows, c_in)
+    buf = ws(n, x.device)
+    lib.fs2_vocoder_post_bwd(code(x.dtype), ptr(x), ptr(wav), ptr(d_wav), rows, seq_len, c_in,
+                             ptr(w), ptr(dx), ptr(dw), ptr(db), ptr(buf), n, stream())
+    return dx
+
+
+def convT_wgrad_fold(dwc, dbc, dw, db, stride):
+    """The phase-form gradient (stride * c_out, c_in, 3) added into the ConvTranspose1d layout
+    dw (c_in, c_out, 2 * stride); db (c_out) += the phase sums of dbc (fs2_convT_wgrad_fold)."""
+    _dev(dwc, dbc, dw, db)
+    _f32("convT_wgrad_fold", dwc, dbc, dw, db)
+    c_in, c_out, k = dw.shape
+    if k != 2 * stride or dwc.numel() != stride * c_out * c_in * 3 or (dbc is None) != (db is None) or \
+            (dbc is not None and (dbc.numel() != stride * c_out or db.numel() != c_out)):
+        raise RuntimeError("convT_wgrad_fold: dwc (stride * c_out, c_in, 3), dw (c_in, c_out, 2 * stride)")
+    lib.fs2_convT_wgrad_fold(ptr(dwc), ptr(dbc), c_in, c_out, stride, ptr(dw), ptr(db), stream())
+
+
+def melspec_bwd(wav, lens, d_mel, hop, window, twiddle, fb, n_mels, n_fft=1024, out=None):
+    """d_wav (B, S), the pull-back of d_mel (B, n_mels, F) through ``melspec``'s mel output
+    (clip and log_mag off; fs2_melspec_bwd).  Operands as ``melspec`` takes them."""
+    first, count, off, w = fb
+    _dev(wav, lens, d_mel, window, twiddle, first, count, off, w, out)
+    _f32("melspec_bwd", wav, d_mel, out)
+    if wav.dim() != 2:
+        raise RuntimeError("melspec_bwd: wav is f32 (B, S)")
+    if lens is not None and (lens.dtype != torch.int64 or lens.numel() != wav.shape[0]):
+        raise RuntimeError("melspec_bwd: lens is int64 (B)")
+    _tables_f32("melspec_bwd", window, twiddle)
+    if (first.dtype, count.dtype, off.dtype, w.dtype) != (torch.int32,) * 3 + (torch.float32,) or \
+            not first.numel() == count.numel() == off.numel() == int(n_mels):
+        raise RuntimeError("melspec_bwd: filterbank is (first, count, offset) int32 (n_mels) + f32 weights")
+    B, S = wav.shape
+    hop = int(hop)
+    F = 1 + S // hop
+    if d_mel.numel() != B * int(n_mels) * F:
+        raise RuntimeError(f"melspec_bwd: d_mel is (B, n_mels, {F})")
+    if out is None:
+        out = torch.empty((B, S), dtype=torch.float32, device=wav.device)
+    elif out.numel() != B * S:
+        raise RuntimeError("melspec_bwd: out is f32 (B, S)")
+    n = lib.fs2_melspec_bwd_ws_bytes(B, S, hop)
+    buf = ws(n, wav.device)
+    lib.fs2_melspec_bwd(ptr(wav), ptr(lens), B, S, int(n_fft), hop, ptr(window), ptr(twiddle),
+                        ptr(first), ptr(count), ptr(off), ptr(w), w.numel(), int(n_mels),
+                        ptr(d_mel), ptr(out), ptr(buf), n, stream())
+    return out
+
+
+def mel_l1(a, b, grad=True):
+    """(loss (1,) = mean |a - b| on the device, d_a = sign(a - b) / N or None) (fs2_mel_l1)."""
+    _dev(a, b)
+    _f32("mel_l1", a, b)
+    if a.numel() != b.numel() or a.numel() == 0:
+        raise RuntimeError("mel_l1: a and b must have the same, non-zero size")
+    loss = torch.empty(1, dtype=torch.float32, device=a.device)
+    d_a = torch.empty(a.shape, dtype=torch.float32, device=a.device) if grad else None
+    n = lib.fs2_mel_l1_ws_bytes()
+    buf = ws(n, a.device)
+    lib.fs2_mel_l1(ptr(a), ptr(b), a.numel(), ptr(loss), ptr(d_a), ptr(buf), n, stream())
+    return loss, d_a
 
 
 # ------------------------------------------------------------------ attention
